@@ -9,6 +9,28 @@ Multi GPU (driver): python -m torch.distributed.run --nnodes=1
                     --gpus N --steps K --warmup W
 
 One JSON line is printed by rank 0 (contract in the project brief).
+
+A plain run does only what the headline figure needs: set up, warm up, time
+`--steps` train steps, print the line.  `--full` is where any measurement
+beyond the headline figure belongs; today there is none, so it adds nothing.
+
+`--dump-outputs DIR` additionally writes what the last timed step computed
+(rank 0) as DIR/<name>.npy, so two builds can be compared output for output.
+Seeds, model init and the synthetic batch are fixed by the arguments, but
+that alone does not make the last step repeatable.  Measured on one MI355X:
+between identical iterations the forward pass, every BatchNorm gradient and
+the whole dx chain are bit-identical, while the weight gradient of each of
+the 53 convolutions varies in its last bf16 bit (MIOpen's tuned
+backward-weights solvers add split-K partial sums atomically, in arrival
+order; the deterministic solvers cost 28 s per step against 0.055 s).  bf16
+SGD on one repeated batch turns that into loss 3.6-4.0 and logits apart by
+hundreds after 40 steps.  So a dumping run puts the model and optimizer back
+to their seeded initial state just before the last timed step (one foreach
+copy inside the timed window): that step runs the same kernels as every
+other, from the same weights in every run, and what is dumped are its
+results that no varying sum feeds: loss, logits, and the stem BatchNorm and
+classifier state after the update (the stem's affine gradient is the end of
+the backward chain through every BN kernel and every conv's dx).
 """
 
 import argparse
@@ -54,6 +76,35 @@ def build_model(name, memory_format, dtype, device, sync, fused=True):
     return model
 
 
+DUMP_MAX_BYTES = 64 << 20  # whole --dump-outputs directory
+# Model state the last step updated, dumped next to the step's own results.
+# No conv weight: its gradient is the one thing that varies from run to run
+# (module docstring).
+DUMP_STATE = ("bn1.weight", "bn1.bias", "bn1.running_mean",
+              "bn1.running_var", "fc.weight")
+
+
+def dump_outputs(dirname, arrays):
+    """Write {name: tensor} as dirname/<name>.npy (float32, or float64 for
+    float64 tensors).  Each array gets an equal share of DUMP_MAX_BYTES; a
+    larger one is cut down to a fixed, seeded sample of its flat elements."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    cap = DUMP_MAX_BYTES // max(len(arrays), 1)
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t.to("cpu", torch.float64 if t.dtype == torch.float64
+                 else torch.float32).contiguous()
+        a = t.numpy()
+        if a.nbytes > cap:
+            idx = np.random.default_rng(0).choice(
+                a.size, size=cap // a.itemsize, replace=False)
+            idx.sort()
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
@@ -72,12 +123,20 @@ def main():
     p.add_argument("--stock", action="store_true",
                    help="use stock torch SyncBatchNorm+DDP (comparison line)")
     p.add_argument("--benchmark", action="store_true",
-                   help="enable MIOpen conv autotune (cudnn.benchmark): ~3%% "
-                        "faster steps but minutes of one-time find cost")
+                   help="enable MIOpen conv autotune (cudnn.benchmark): "
+                        "minutes of find cost in every process; only for "
+                        "configs the shipped find-db does not cover")
     p.add_argument("--graph", action="store_true",
                    help="capture the train step in a hipGraph (single GPU)")
     p.add_argument("--no-fused", action="store_true",
                    help="disable the fused BN(+add)+ReLU epilogue modules")
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="after the timed steps, write the last step's loss "
+                        "and logits and the model state it updated as "
+                        "DIR/<name>.npy (rank 0)")
+    p.add_argument("--full", action="store_true",
+                   help="also run every measurement beyond the headline "
+                        "figure (none today: same as a plain run)")
     p.add_argument("--local_rank", "--local-rank", type=int,
                    default=int(os.environ.get("LOCAL_RANK", 0)),
                    dest="local_rank")
@@ -85,23 +144,19 @@ def main():
 
     # In-tree MIOpen find-db (miopen_db/, exported by
     # tools/export_miopen_finddb.sh after a --benchmark run): tuned conv
-    # solver choices ship with the repo, so find-mode lookups hit the cache
-    # instead of re-running the exhaustive search.  Auto-enable autotune for
-    # the exact tuned config (resnet50 bf16 CL bs512 — the headline bench:
-    # measured 9372 vs 8384 img/s, +11.8%); other configs opt in with
-    # --benchmark (a db miss falls back to a one-time exhaustive find).
+    # solver choices ship with the repo.  MIOpen's immediate mode (the
+    # default, cudnn.benchmark off) picks each conv's solver from this db, so
+    # the tuned config (resnet50 bf16 CL bs512 — the headline bench) runs the
+    # tuned solvers from its first step.  Autotune is NOT auto-enabled: the
+    # find re-measures every solver of every conv in each new process even
+    # when the db has the record (~120 s before the first step, measured)
+    # and rewrites the db files, for the same steady-state step time
+    # (A/B in profiles/r02_kernel_polish.md §9).  --benchmark opts in, to
+    # tune another config or to refresh the db.
     _db = os.path.join(os.path.dirname(os.path.abspath(__file__)),
                        "miopen_db")
     if os.path.isdir(_db) and os.listdir(_db):
         os.environ.setdefault("MIOPEN_USER_DB_PATH", _db)
-        tuned_cfg = (
-            args.model == "resnet50" and args.batch_size == 512
-            and args.memory_format == "channels_last"
-            and args.dtype == "bf16"
-            and os.environ.get("MSBN_NO_AUTOTUNE", "0") != "1"
-        )
-        if tuned_cfg:
-            args.benchmark = True
     if args.benchmark:
         torch.backends.cudnn.benchmark = True  # MIOpen conv autotune
 
@@ -165,6 +220,23 @@ def main():
                 )
         model.train()
 
+        # --dump-outputs: the seeded initial state, put back before the last
+        # timed step so that step starts from the same weights in every run
+        restore = None
+        if args.dump_outputs:
+            core = getattr(model, "module", model)
+            live = list(core.parameters()) + list(core.buffers())
+            init = [t.detach().clone() for t in live]
+
+            def restore():
+                with torch.no_grad():
+                    torch._foreach_copy_(live, init)
+                    # zeroed momentum == no momentum yet: buf = 0.9*0 + grad
+                    bufs = [st["momentum_buffer"] for st in opt.state.values()
+                            if st.get("momentum_buffer") is not None]
+                    if bufs:
+                        torch._foreach_zero_(bufs)
+
         try:  # fused foreach SGD (works on ROCm; identical for both impls)
             opt = torch.optim.SGD(model.parameters(), lr=0.1, momentum=0.9,
                                   weight_decay=1e-4, fused=True)
@@ -185,7 +257,7 @@ def main():
             loss = loss_fn(out.float(), y)
             loss.backward()
             opt.step()
-            return loss
+            return loss.detach(), out.detach()
 
         # warmup (on the side stream when graphing: allocator steady state,
         # MIOpen finds, RCCL communicator creation)
@@ -226,11 +298,15 @@ def main():
         torch.cuda.synchronize()
     t0 = time.perf_counter()
     if graph is not None:
-        for _ in range(args.steps):
-            graph.replay()
+        for i in range(args.steps):
+            if restore is not None and i == args.steps - 1:
+                restore()
+            graph.replay()  # rewrites the captured `loss` and `out` in place
     else:
-        for _ in range(args.steps):
-            step()
+        for i in range(args.steps):
+            if restore is not None and i == args.steps - 1:
+                restore()
+            loss, out = step()
     if use_cuda:
         torch.cuda.synchronize()
     if distributed:
@@ -247,6 +323,12 @@ def main():
     n_gpus = world_size
     images_per_sec = bs * n_gpus * args.steps / elapsed
     ms_per_step = 1000.0 * elapsed / args.steps
+
+    if args.dump_outputs and rank == 0:
+        state = getattr(model, "module", model).state_dict()
+        arrays = {"loss": loss.reshape(1), "logits": out}
+        arrays.update((k.replace(".", "_"), state[k]) for k in DUMP_STATE)
+        dump_outputs(args.dump_outputs, arrays)
 
     if rank == 0:
         print(json.dumps({

@@ -13,9 +13,10 @@ REQUIRED_KEYS = {
 }
 
 
-def _run_bench(extra):
+def _run_bench(extra, env_extra=None):
     env = dict(os.environ)
     env["PYTHONPATH"] = REPO
+    env.update(env_extra or {})
     r = subprocess.run(
         [sys.executable, os.path.join(REPO, "bench.py")] + extra,
         capture_output=True, text=True, timeout=600, env=env, cwd=REPO,
@@ -38,6 +39,48 @@ def test_bench_json_contract_cpu():
     assert out["value"] > 0 and out["ms_per_step"] > 0
     assert out["config"]["global_batch"] == 2
     assert out["config"]["parallelism"] == "dp1"
+
+
+def test_bench_dump_outputs_cpu(tmp_path):
+    """--dump-outputs writes the last timed step's results as float .npy
+    files, the same from run to run.  A dumping run puts the seeded initial
+    state back before its last timed step, so the files do not depend on
+    how many steps came before it: 1 warmup + 2 steps dumps exactly what a
+    single first step dumps.  --full is accepted and leaves the result
+    line's meaning alone."""
+    import numpy as np
+
+    cfg = ["--gpus", "1", "--batch-size", "2", "--model", "resnet18",
+           "--dtype", "fp32", "--memory-format", "contiguous"]
+    a, b = str(tmp_path / "a"), str(tmp_path / "b")
+    # Bit-equality needs a deterministic run: hide any GPU (its conv
+    # backward-weights kernels sum in a varying order), one CPU thread.
+    one = {"HIP_VISIBLE_DEVICES": "-1", "CUDA_VISIBLE_DEVICES": "-1",
+           "OMP_NUM_THREADS": "1", "MKL_NUM_THREADS": "1"}
+    out = _run_bench(cfg + ["--steps", "2", "--warmup", "1",
+                            "--dump-outputs", a], one)
+    full = _run_bench(cfg + ["--steps", "1", "--warmup", "0", "--full",
+                             "--dump-outputs", b], one)
+    assert REQUIRED_KEYS.issubset(full.keys())
+    for k in ("metric", "unit", "higher_is_better", "dtype"):
+        assert full[k] == out[k]
+    assert out["steps"] == 2 and full["steps"] == 1
+    names = sorted(os.listdir(a))
+    assert names == sorted(os.listdir(b))
+    assert {"loss.npy", "logits.npy", "bn1_weight.npy",
+            "fc_weight.npy"}.issubset(names)
+    total = 0
+    for n in names:
+        x, y = np.load(os.path.join(a, n)), np.load(os.path.join(b, n))
+        assert x.dtype in (np.float32, np.float64)
+        assert np.isfinite(x).all()
+        assert np.array_equal(x, y), n
+        total += x.nbytes
+    assert total <= 64 << 20
+    assert np.load(os.path.join(a, "logits.npy")).shape == (2, 1000)
+    assert np.load(os.path.join(a, "loss.npy")).shape == (1,)
+    # the dumped step did update the model: affine BN weight starts at 1
+    assert not np.all(np.load(os.path.join(a, "bn1_weight.npy")) == 1.0)
 
 
 def test_bench_distributed_launch_cpu():
