@@ -44,6 +44,15 @@ def main():
                         "best for detection shapes on this stack, and stock "
                         "torch-ROCm SEGFAULTS on bf16+channels_last here — "
                         "profiles/r02_kernel_polish.md §6)")
+    p.add_argument("--frozen-backbone", action="store_true",
+                   help="freeze every backbone BatchNorm (fixed statistics "
+                        "and affine: the detection fine-tuning recipe).  "
+                        "With --stock the converted backbone BNs run in eval "
+                        "mode with requires_grad=False: identical math")
+    p.add_argument("--fused-backbone", action="store_true",
+                   help="build the backbone with the fused BN(+add)+ReLU "
+                        "epilogues (msbn only; --stock has no fused modules "
+                        "and keeps the unfused backbone)")
     p.add_argument("--local_rank", "--local-rank", type=int,
                    default=int(os.environ.get("LOCAL_RANK", 0)),
                    dest="local_rank")
@@ -81,12 +90,21 @@ def main():
     if args.stock:
         from msbn.models import convert_to_torch_batchnorm
 
-        model = convert_to_torch_batchnorm(msbn.models.retinanet())
+        model = convert_to_torch_batchnorm(msbn.models.retinanet(
+            frozen_backbone=args.frozen_backbone))
         if world > 1:
-            model = torch.nn.SyncBatchNorm.convert_sync_batchnorm(model)
+            # the stock converter would un-freeze the backbone: heads only
+            conv = torch.nn.SyncBatchNorm.convert_sync_batchnorm
+            if args.frozen_backbone:
+                model.cls_head = conv(model.cls_head)
+                model.box_head = conv(model.box_head)
+            else:
+                model = conv(model)
         model = model.to(device)
     else:
-        model = msbn.convert_sync_batchnorm(msbn.models.retinanet()).to(device)
+        model = msbn.convert_sync_batchnorm(msbn.models.retinanet(
+            frozen_backbone=args.frozen_backbone,
+            fused_backbone=args.fused_backbone)).to(device)
     dtype = torch.bfloat16 if (args.dtype == "bf16" and use_cuda) else \
         torch.float32
     if dtype == torch.bfloat16:
@@ -187,6 +205,9 @@ def main():
                        "hip_graph": graph is not None,
                        "memory_format": "channels_last" if args.channels_last
                        else "contiguous",
+                       "frozen_backbone": args.frozen_backbone,
+                       "fused_backbone": args.fused_backbone
+                       and not args.stock,
                        "impl": "stock" if args.stock else "msbn"},
         }))
     if world > 1:

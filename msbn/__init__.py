@@ -22,5 +22,6 @@ __version__ = "0.1.0"
 from msbn import nn, ops, parallel, data, models, utils  # noqa: F401
 
 from msbn.nn import SyncBatchNorm, convert_sync_batchnorm  # noqa: F401
+from msbn.nn import FrozenBatchNorm2d, freeze_batchnorm  # noqa: F401
 from msbn.parallel import DistributedDataParallel  # noqa: F401
 from msbn.data import DistributedSampler  # noqa: F401

@@ -67,10 +67,17 @@ class Head(nn.Module):
 
 
 class RetinaNet(nn.Module):
-    def __init__(self, num_classes: int = 80):
+    def __init__(self, num_classes: int = 80, frozen_backbone: bool = False,
+                 fused_backbone: bool = False):
         super().__init__()
-        self.backbone = resnet50()
+        self.backbone = resnet50(fused=True) if fused_backbone else resnet50()
         del self.backbone.fc, self.backbone.avgpool
+        if frozen_backbone:
+            # detection fine-tuning recipe: backbone BN statistics and affine
+            # are fixed; the heads below keep trainable, sync-able BN
+            from msbn.nn import freeze_batchnorm
+
+            self.backbone = freeze_batchnorm(self.backbone)
         self.fpn = FPN([512, 1024, 2048], 256)
         self.cls_head = Head(256, num_classes)
         self.box_head = Head(256, 4)

@@ -7,9 +7,17 @@ from msbn.nn.batchnorm import (  # noqa: F401
 )
 from msbn.nn.functions import SyncBatchNormFunction  # noqa: F401
 from msbn.nn.fused import SyncBatchNormAct2d, SyncBatchNormActFunction  # noqa: F401
+from msbn.nn.frozen import (  # noqa: F401
+    FrozenBatchNorm2d,
+    FrozenBatchNormActFunction,
+    freeze_batchnorm,
+)
 from msbn.nn.fuse_pass import fuse_bn_act  # noqa: F401
 
 __all__ = [
+    "FrozenBatchNorm2d",
+    "FrozenBatchNormActFunction",
+    "freeze_batchnorm",
     "BatchNorm1d",
     "BatchNorm2d",
     "BatchNorm3d",

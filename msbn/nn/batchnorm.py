@@ -17,6 +17,7 @@ Differences from stock, by design (documented, not accidental):
     no GPU->CPU sync per layer and safe under hipGraph capture.
 """
 
+import os
 from typing import Optional
 
 import torch
@@ -25,6 +26,11 @@ from torch import Tensor
 from torch.nn import Module, Parameter, init
 
 from msbn.nn.functions import SyncBatchNormFunction
+
+# A/B measurement knob (read once at import, like MSBN_AB_NONT): keep the
+# composed eager expression on the GPU running-stats path with autograd on,
+# i.e. the behaviour before the frozen kernels existed.
+_FROZEN_COMPOSED = os.environ.get("MSBN_FROZEN_COMPOSED", "0") == "1"
 
 
 class _NormBase(Module):
@@ -164,6 +170,68 @@ def _momentum_factor(module) -> float:
     return module.momentum
 
 
+def _composed_running_stats_forward(
+    input: Tensor, residual: Optional[Tensor], weight, bias, running_mean,
+    running_var, eps: float, relu: bool,
+) -> Tensor:
+    """Differentiable eager expression of relu?(bn_running(x) [+ residual]):
+    the CPU path, and the GPU A/B baseline under MSBN_FROZEN_COMPOSED=1."""
+    rm = running_mean.to(torch.float32)
+    rv = running_var.to(torch.float32)
+    invstd = torch.rsqrt(rv + eps)
+    scale = invstd
+    shift = -rm * invstd
+    if weight is not None:
+        wf = weight.to(torch.float32)
+        scale = scale * wf
+        shift = shift * wf
+    if bias is not None:
+        shift = shift + bias.to(torch.float32)
+    shape = [1] * input.dim()
+    shape[1] = input.shape[1]
+    out = input.to(torch.float32) * scale.reshape(shape) + shift.reshape(shape)
+    if residual is not None:
+        out = out + residual.to(torch.float32)
+    if relu:
+        out = torch.relu(out)
+    return out.to(input.dtype)
+
+
+def _running_stats_forward(
+    module, input: Tensor, residual: Optional[Tensor], relu: bool
+) -> Tensor:
+    """Normalize with the module's running statistics (eval mode / frozen):
+
+      * GPU, autograd on  -> FrozenBatchNormActFunction (coefs kernel + one
+        elemt launch forward, one elementwise kernel backward);
+      * GPU, ``no_grad``  -> one fused elemt kernel (inference serving);
+      * CPU               -> the composed differentiable expression.
+    """
+    if input.is_cuda and not torch.is_grad_enabled():
+        from msbn import ops as _ops
+        from msbn.nn.functions import _contig, _match_layout
+
+        input = _contig(input)
+        if residual is not None:
+            residual = _match_layout(residual, input)
+        rm = module.running_mean.to(torch.float32)
+        invstd = torch.rsqrt(module.running_var.to(torch.float32) + module.eps)
+        return _ops.batch_norm_elemt_act(
+            input, residual, module.weight, module.bias, rm, invstd, relu
+        )
+    if input.is_cuda and not _FROZEN_COMPOSED:
+        from msbn.nn.frozen import FrozenBatchNormActFunction
+
+        return FrozenBatchNormActFunction.apply(
+            input, residual, module.weight, module.bias, module.running_mean,
+            module.running_var, module.eps, relu,
+        )
+    return _composed_running_stats_forward(
+        input, residual, module.weight, module.bias, module.running_mean,
+        module.running_var, module.eps, relu,
+    )
+
+
 def _batch_norm_forward(module, input: Tensor, sync: bool) -> Tensor:
     if input.dim() < 2:
         raise ValueError(f"expected at least 2D input (got {input.dim()}D input)")
@@ -180,33 +248,7 @@ def _batch_norm_forward(module, input: Tensor, sync: bool) -> Tensor:
     )
 
     if not bn_training:
-        # Eval fast path: fused elemt kernel when no autograd is needed
-        # (inference serving); composed differentiable expression otherwise.
-        if input.is_cuda and not torch.is_grad_enabled():
-            from msbn import ops as _ops
-            from msbn.nn.functions import _contig
-
-            input = _contig(input)
-            rm = module.running_mean.to(torch.float32)
-            invstd = torch.rsqrt(module.running_var.to(torch.float32) + module.eps)
-            return _ops.batch_norm_elemt_act(
-                input, None, module.weight, module.bias, rm, invstd, False
-            )
-        rm = module.running_mean.to(torch.float32)
-        rv = module.running_var.to(torch.float32)
-        invstd = torch.rsqrt(rv + module.eps)
-        scale = invstd
-        shift = -rm * invstd
-        if module.weight is not None:
-            wf = module.weight.to(torch.float32)
-            scale = scale * wf
-            shift = shift * wf
-        if module.bias is not None:
-            shift = shift + module.bias.to(torch.float32)
-        shape = [1] * input.dim()
-        shape[1] = input.shape[1]
-        out = input.to(torch.float32) * scale.reshape(shape) + shift.reshape(shape)
-        return out.to(input.dtype)
+        return _running_stats_forward(module, input, None, False)
 
     process_group = None
     world_size = 1
@@ -297,7 +339,12 @@ class SyncBatchNorm(_NormBase):
         """
         module_output = module
         targets = (torch.nn.modules.batchnorm._BatchNorm, _NormBase)
-        if isinstance(module, targets) and not isinstance(module, SyncBatchNorm):
+        # frozen modules have no batch statistics to sync: left in place
+        if (
+            isinstance(module, targets)
+            and not isinstance(module, SyncBatchNorm)
+            and not getattr(module, "_msbn_frozen", False)
+        ):
             module_output = SyncBatchNorm(
                 module.num_features,
                 module.eps,

@@ -1,6 +1,7 @@
 """fuse_bn_act: graph-free module-tree pass that merges adjacent
 (BatchNorm2d | SyncBatchNorm, ReLU) pairs inside nn.Sequential containers
 into a single SyncBatchNormAct2d (one-kernel epilogue, identical math).
+A (FrozenBatchNorm2d, ReLU) pair becomes a FrozenBatchNorm2d(relu=True).
 
 Works on any model whose BN+ReLU pairs live in Sequentials (DCGAN,
 torchvision-style stems, custom CNNs).  Residual-add fusion requires the
@@ -13,10 +14,14 @@ blocks) and is not attempted here.
 import torch.nn as nn
 
 from msbn.nn.batchnorm import SyncBatchNorm, _BatchNorm
+from msbn.nn.frozen import FrozenBatchNorm2d, _frozen_from
 from msbn.nn.fused import SyncBatchNormAct2d
 
 
-def _to_act(bn, relu_module) -> SyncBatchNormAct2d:
+def _to_act(bn, relu_module):
+    if isinstance(bn, FrozenBatchNorm2d):
+        # frozen stays frozen: same tensors, ReLU folded into the epilogue
+        return _frozen_from(bn, relu=isinstance(relu_module, nn.ReLU))
     out = SyncBatchNormAct2d(
         bn.num_features, bn.eps, bn.momentum, bn.affine,
         bn.track_running_stats,
@@ -36,6 +41,8 @@ def _to_act(bn, relu_module) -> SyncBatchNormAct2d:
 def _fusable_bn(m) -> bool:
     if isinstance(m, SyncBatchNormAct2d):
         return False
+    if isinstance(m, FrozenBatchNorm2d):
+        return not m.relu
     return isinstance(m, (SyncBatchNorm, _BatchNorm, nn.modules.batchnorm._BatchNorm))
 
 

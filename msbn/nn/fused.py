@@ -17,7 +17,8 @@ import torch
 import torch.distributed as dist
 
 from msbn import ops
-from msbn.nn.batchnorm import SyncBatchNorm, _momentum_factor
+from msbn.nn.batchnorm import (SyncBatchNorm, _momentum_factor,
+                               _running_stats_forward)
 from msbn.nn.functions import (_combined_view, _contig, _force_sync,
                                _match_layout, compute_sync_stats)
 
@@ -234,42 +235,7 @@ class SyncBatchNormAct2d(SyncBatchNorm):
         )
 
         if not bn_training:
-            # eval fast path: one fused kernel under no_grad (serving)
-            if input.is_cuda and not torch.is_grad_enabled():
-                from msbn import ops as _ops
-
-                input = _contig(input)
-                if residual is not None:
-                    residual = _match_layout(residual, input)
-                rm = self.running_mean.to(torch.float32)
-                invstd = torch.rsqrt(
-                    self.running_var.to(torch.float32) + self.eps
-                )
-                return _ops.batch_norm_elemt_act(
-                    input, residual, self.weight, self.bias, rm, invstd,
-                    self.relu,
-                )
-            # composed (differentiable) path
-            rm = self.running_mean.to(torch.float32)
-            rv = self.running_var.to(torch.float32)
-            invstd = torch.rsqrt(rv + self.eps)
-            scale = invstd
-            shift = -rm * invstd
-            if self.weight is not None:
-                wf = self.weight.to(torch.float32)
-                scale = scale * wf
-                shift = shift * wf
-            if self.bias is not None:
-                shift = shift + self.bias.to(torch.float32)
-            shape = [1] * input.dim()
-            shape[1] = input.shape[1]
-            out = input.to(torch.float32) * scale.reshape(shape) + \
-                shift.reshape(shape)
-            if residual is not None:
-                out = out + residual.to(torch.float32)
-            if self.relu:
-                out = torch.relu(out)
-            return out.to(input.dtype)
+            return _running_stats_forward(self, input, residual, self.relu)
 
         process_group = None
         world_size = 1

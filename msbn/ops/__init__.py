@@ -250,8 +250,42 @@ def batch_norm_backward_elemt_act(grad_out, input, residual, mean, invstd,
     )
 
 
+def bn_frozen_coefs(running_mean, running_var, eps: float, weight, bias):
+    """Packed fp32 [scale(C) | shift(C)] from FIXED running statistics in one
+    launch: scale = weight*rsqrt(running_var+eps), shift = bias -
+    running_mean*scale.  The buffer is what ``batch_norm_elemt_act(coefs=)``
+    and ``batch_norm_frozen_backward_elemt`` consume."""
+    if running_mean.is_cuda:
+        return _require_hip().bn_frozen_coefs(
+            running_mean, running_var, eps, weight, bias
+        )
+    return _ref.bn_frozen_coefs(running_mean, running_var, eps, weight, bias)
+
+
+def batch_norm_frozen_backward_elemt(grad_out, input, residual, coefs,
+                                     relu_mask: bool, want_input_grad: bool,
+                                     want_res_grad: bool):
+    """Backward of the frozen BN(+add)(+ReLU) epilogue, one elementwise pass:
+    dx = scale*g, dres = g, g = grad_out*1[z>0].  ``input`` / ``residual``
+    are only needed for the gate (``relu_mask``); without it ``dres`` is
+    ``grad_out`` itself.  Returns (dx-or-None, dres-or-None)."""
+    if grad_out.is_cuda:
+        dx, dres = _require_hip().batch_norm_frozen_backward_elemt(
+            grad_out, input, residual, coefs, relu_mask, want_input_grad,
+            want_res_grad,
+        )
+        return (dx if want_input_grad else None,
+                dres if want_res_grad else None)
+    return _ref.batch_norm_frozen_backward_elemt(
+        grad_out, input, residual, coefs, relu_mask, want_input_grad,
+        want_res_grad,
+    )
+
+
 __all__ = [
     "hip_available",
+    "bn_frozen_coefs",
+    "batch_norm_frozen_backward_elemt",
     "batch_norm_elemt_act",
     "bn_make_coefs",
     "batch_norm_backward_reduce_act",

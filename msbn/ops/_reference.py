@@ -194,6 +194,36 @@ def batch_norm_backward_elemt_act(
     return dx, dres
 
 
+def bn_frozen_coefs(running_mean, running_var, eps: float, weight, bias):
+    """Packed fp32 [scale(C) | shift(C)] from fixed running statistics:
+    scale = weight / sqrt(running_var + eps), shift = bias - running_mean*scale."""
+    invstd = torch.rsqrt(running_var.to(torch.float32) + eps)
+    scale, shift = _act_coefs(running_mean, invstd, weight, bias)
+    return torch.cat([scale, shift])
+
+
+def batch_norm_frozen_backward_elemt(
+    grad_out, input, residual, coefs, relu_mask: bool,
+    want_input_grad: bool, want_res_grad: bool,
+):
+    """Backward of y = relu?(x*scale + shift [+ residual]) with FIXED scale /
+    shift: dx = scale*g, dres = g, g = grad_out * 1[z > 0].  ``input`` and
+    ``residual`` are only consulted for the gate (relu_mask)."""
+    C = grad_out.shape[1]
+    scale = _chan_view(coefs[:C], grad_out)
+    g = grad_out.to(torch.float32)
+    if relu_mask:
+        z = input.to(torch.float32) * scale + _chan_view(coefs[C:], grad_out)
+        if residual is not None:
+            z = z + residual.to(torch.float32)
+        g = torch.where(z > 0, g, torch.zeros_like(g))
+    dx = (g * scale).to(grad_out.dtype) if want_input_grad else None
+    dres = None
+    if want_res_grad:
+        dres = g.to(grad_out.dtype) if relu_mask else grad_out
+    return dx, dres
+
+
 def batch_norm_backward_reduce(
     grad_out: torch.Tensor,
     input: torch.Tensor,

@@ -788,6 +788,134 @@ __global__ void bn_bwd_elemt_nhwc(const T* __restrict__ dy,
 }
 
 // =====================================================================
+// frozen path: the statistics are the (fixed) running stats, so there is no
+// batch reduction anywhere.  One tiny kernel folds (running_mean,
+// running_var, eps, weight, bias) into the packed [scale | shift] buffer the
+// forward elemt kernels consume; backward is ONE elementwise pass
+//   dx = scale[c]*g,  dres = g,  g = dy * 1[z > 0]
+// with the ReLU gate recomputed from (x, scale, shift[, res]) exactly as
+// bn_bwd_elemt_* does.  Without the gate (!MASK) x is never read, so the
+// layer does not have to keep its input alive.
+// =====================================================================
+template <typename RT, typename WT>
+__global__ void bn_frozen_coefs(const RT* __restrict__ rmean,
+                                const RT* __restrict__ rvar, float eps,
+                                const WT* __restrict__ w,
+                                const WT* __restrict__ b, int64_t C,
+                                float* __restrict__ scale,
+                                float* __restrict__ shift) {
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  const float istd = (float)rsqrt((double)to_f(rvar[c]) + (double)eps);
+  const float sc = istd * (w != nullptr ? to_f(w[c]) : 1.f);
+  scale[c] = sc;
+  shift[c] = -to_f(rmean[c]) * sc + (b != nullptr ? to_f(b[c]) : 0.f);
+}
+
+// x / res are only dereferenced when MASK (the host passes nullptr
+// otherwise); dx may be nullptr when only the residual branch needs its
+// gradient (wave-uniform branch).
+template <typename T, int V, bool MASK, bool RES, bool RESG>
+__global__ void bn_frozen_bwd_elemt_nchw(const T* __restrict__ dy,
+                                         const T* __restrict__ x,
+                                         const T* __restrict__ res,
+                                         T* __restrict__ dx,
+                                         T* __restrict__ dres,
+                                         const float* __restrict__ scale,
+                                         const float* __restrict__ shift,
+                                         int64_t total, int64_t C, int64_t S) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+       i * V < total; i += stride) {
+    const int64_t e = i * V;
+    const int64_t c = (e / S) % C;
+    const float sc = scale[c];
+    const float sh = MASK ? shift[c] : 0.f;
+    if (V == 1) {
+      float g = to_f(nt_load1(&dy[e]));
+      if (MASK) {
+        float z = sc * to_f(nt_load1(&x[e])) + sh;
+        if (RES) z += to_f(nt_load1(&res[e]));
+        if (z <= 0.f) g = 0.f;
+      }
+      if (dx != nullptr) nt_store1(&dx[e], from_f<T>(sc * g));
+      if (RESG) nt_store1(&dres[e], from_f<T>(g));
+    } else {
+      Pack<T, V> pg = nt_load<T, V>(&dy[e]);
+      Pack<T, V> px, pr;
+      if (MASK) px = nt_load<T, V>(&x[e]);
+      if (MASK && RES) pr = nt_load<T, V>(&res[e]);
+      Pack<T, V> po, pq;
+#pragma unroll
+      for (int k = 0; k < V; ++k) {
+        float g = to_f(pg.v[k]);
+        if (MASK) {
+          float z = sc * to_f(px.v[k]) + sh;
+          if (RES) z += to_f(pr.v[k]);
+          if (z <= 0.f) g = 0.f;
+        }
+        po.v[k] = from_f<T>(sc * g);
+        if (RESG) pq.v[k] = from_f<T>(g);
+      }
+      if (dx != nullptr) nt_store<T, V>(&dx[e], po);
+      if (RESG) nt_store<T, V>(&dres[e], pq);
+    }
+  }
+}
+
+template <typename T, int V, bool MASK, bool RES, bool RESG>
+__global__ void bn_frozen_bwd_elemt_nhwc(const T* __restrict__ dy,
+                                         const T* __restrict__ x,
+                                         const T* __restrict__ res,
+                                         T* __restrict__ dx,
+                                         T* __restrict__ dres,
+                                         const float* __restrict__ scale,
+                                         const float* __restrict__ shift,
+                                         int64_t total, int64_t C) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+       i * V < total; i += stride) {
+    const int64_t e = i * V;
+    const int64_t c = e % C;
+    if (V == 1) {
+      float g = to_f(nt_load1(&dy[e]));
+      const float sc = scale[c];
+      if (MASK) {
+        float z = sc * to_f(nt_load1(&x[e])) + shift[c];
+        if (RES) z += to_f(nt_load1(&res[e]));
+        if (z <= 0.f) g = 0.f;
+      }
+      if (dx != nullptr) nt_store1(&dx[e], from_f<T>(sc * g));
+      if (RESG) nt_store1(&dres[e], from_f<T>(g));
+    } else {
+      Pack<T, V> pg = nt_load<T, V>(&dy[e]);
+      Pack<float, V> psc = *reinterpret_cast<const Pack<float, V>*>(&scale[c]);
+      Pack<float, V> psh;
+      Pack<T, V> px, pr;
+      if (MASK) {
+        psh = *reinterpret_cast<const Pack<float, V>*>(&shift[c]);
+        px = nt_load<T, V>(&x[e]);
+      }
+      if (MASK && RES) pr = nt_load<T, V>(&res[e]);
+      Pack<T, V> po, pq;
+#pragma unroll
+      for (int k = 0; k < V; ++k) {
+        float g = to_f(pg.v[k]);
+        if (MASK) {
+          float z = psc.v[k] * to_f(px.v[k]) + psh.v[k];
+          if (RES) z += to_f(pr.v[k]);
+          if (z <= 0.f) g = 0.f;
+        }
+        po.v[k] = from_f<T>(psc.v[k] * g);
+        if (RESG) pq.v[k] = from_f<T>(g);
+      }
+      if (dx != nullptr) nt_store<T, V>(&dx[e], po);
+      if (RESG) nt_store<T, V>(&dres[e], pq);
+    }
+  }
+}
+
+// =====================================================================
 // small-plane world-1 fused kernels (the stock K10-style single-launch
 // family, MI355X-gated): block-per-channel, TWO passes over an L2-resident
 // plane.  Used when plane = N*S is small (GAN / small-per-GPU-batch
@@ -1781,6 +1909,150 @@ at::Tensor batch_norm_backward_elemt(
   return std::get<0>(batch_norm_backward_elemt_act(
       grad_out, input, c10::nullopt, mean, invstd, weight, c10::nullopt,
       sum_dy, sum_dy_xmu, count, false, false, c10::nullopt));
+}
+
+// ---------------------------------------------------------------------------
+// frozen path (running-stat normalization with autograd on)
+// ---------------------------------------------------------------------------
+at::Tensor bn_frozen_coefs(const at::Tensor& running_mean,
+                           const at::Tensor& running_var, double eps,
+                           const c10::optional<at::Tensor>& weight,
+                           const c10::optional<at::Tensor>& bias) {
+  const int64_t C = running_mean.numel();
+  TORCH_CHECK(running_mean.dim() == 1 && running_mean.is_contiguous() &&
+                  running_var.is_contiguous() &&
+                  running_var.sizes() == running_mean.sizes() &&
+                  running_var.scalar_type() == running_mean.scalar_type(),
+              "bn_frozen_coefs: running_mean / running_var must be matching "
+              "contiguous [C] tensors");
+  const bool has_w = weight.has_value() && weight->defined();
+  const bool has_b = bias.has_value() && bias->defined();
+  TORCH_CHECK(!has_w || (weight->numel() == C && weight->is_contiguous()),
+              "bn_frozen_coefs: weight must be contiguous [C]");
+  TORCH_CHECK(!has_b || (bias->numel() == C && bias->is_contiguous()),
+              "bn_frozen_coefs: bias must be contiguous [C]");
+  TORCH_CHECK(!has_w || !has_b ||
+                  weight->scalar_type() == bias->scalar_type(),
+              "bn_frozen_coefs: weight and bias dtypes differ");
+  auto coefs = at::empty({2 * C}, running_mean.options().dtype(at::kFloat));
+  if (C == 0) return coefs;
+  float* scale = coefs.data_ptr<float>();
+  float* shift = scale + C;
+  auto stream = cur_stream();
+  const int cgrid = (int)cdiv(C, MSBN_BLOCK);
+  const auto w_type = has_w   ? weight->scalar_type()
+                      : has_b ? bias->scalar_type()
+                              : at::kFloat;
+  MSBN_DISPATCH_RSTAT(running_mean.scalar_type(), "bn_frozen_coefs", [&] {
+    MSBN_DISPATCH_WTYPE(w_type, "bn_frozen_coefs", [&] {
+      const rstat_t* rm =
+          reinterpret_cast<const rstat_t*>(running_mean.data_ptr());
+      const rstat_t* rv =
+          reinterpret_cast<const rstat_t*>(running_var.data_ptr());
+      const wt_t* wp =
+          has_w ? reinterpret_cast<const wt_t*>(weight->data_ptr()) : nullptr;
+      const wt_t* bp =
+          has_b ? reinterpret_cast<const wt_t*>(bias->data_ptr()) : nullptr;
+      hipLaunchKernelGGL((bn_frozen_coefs<rstat_t, wt_t>), dim3(cgrid),
+                         dim3(MSBN_BLOCK), 0, stream, rm, rv, (float)eps, wp,
+                         bp, C, scale, shift);
+    });
+  });
+  return coefs;
+}
+
+std::tuple<at::Tensor, at::Tensor> batch_norm_frozen_backward_elemt(
+    const at::Tensor& grad_out, const c10::optional<at::Tensor>& input,
+    const c10::optional<at::Tensor>& residual, const at::Tensor& coefs,
+    bool relu_mask, bool want_input_grad, bool want_res_grad) {
+  TORCH_CHECK(grad_out.dim() >= 2,
+              "batch_norm_frozen_backward_elemt: grad_out must be >= 2-D");
+  const Layout L = get_layout(grad_out);
+  // every tensor is indexed with grad_out's dense layout
+  auto same_layout = [&](const at::Tensor& t) {
+    if (t.sizes() != grad_out.sizes() ||
+        t.scalar_type() != grad_out.scalar_type())
+      return false;
+    if (t.strides() == grad_out.strides()) return true;
+    if (!L.nhwc) return t.is_contiguous();
+    return t.is_contiguous(grad_out.dim() == 4
+                               ? at::MemoryFormat::ChannelsLast
+                               : at::MemoryFormat::ChannelsLast3d);
+  };
+  const bool has_x = input.has_value() && input->defined();
+  const bool has_res = relu_mask && residual.has_value() && residual->defined();
+  TORCH_CHECK(!relu_mask || has_x,
+              "batch_norm_frozen_backward_elemt: relu_mask needs the input");
+  TORCH_CHECK(!relu_mask || same_layout(*input),
+              "input must match grad_out shape/strides/dtype");
+  TORCH_CHECK(!has_res || same_layout(*residual),
+              "residual must match grad_out shape/strides/dtype");
+  TORCH_CHECK(coefs.scalar_type() == at::kFloat && coefs.is_contiguous() &&
+                  coefs.numel() == 2 * L.C,
+              "coefs must be contiguous fp32 [2C] ([scale | shift])");
+
+  at::Tensor dx, dres;
+  // without the gate the residual branch's gradient IS grad_out
+  const bool resg = want_res_grad && relu_mask;
+  if (want_res_grad && !relu_mask) dres = grad_out;
+  if (want_input_grad) dx = at::empty_like(grad_out);
+  if (resg) dres = at::empty_like(grad_out);
+  if (grad_out.numel() == 0 || (!want_input_grad && !resg)) return {dx, dres};
+
+  auto stream = cur_stream();
+  const float* scale = coefs.data_ptr<float>();
+  const float* shift = scale + L.C;
+  const int64_t total = grad_out.numel();
+  MSBN_DISPATCH_FLOAT_TYPES(grad_out.scalar_type(), "bn_frozen_bwd_elemt", [&] {
+    const native_t* dy =
+        reinterpret_cast<const native_t*>(grad_out.data_ptr<scalar_t>());
+    const native_t* x =
+        relu_mask ? reinterpret_cast<const native_t*>(input->data_ptr())
+                  : nullptr;
+    const native_t* res =
+        has_res ? reinterpret_cast<const native_t*>(residual->data_ptr())
+                : nullptr;
+    native_t* o = want_input_grad
+                      ? reinterpret_cast<native_t*>(dx.data_ptr<scalar_t>())
+                      : nullptr;
+    native_t* dr =
+        resg ? reinterpret_cast<native_t*>(dres.data_ptr<scalar_t>())
+             : nullptr;
+    constexpr int VMAX = 16 / (int)sizeof(native_t);
+    const int64_t inner = L.nhwc ? L.C : L.S;
+    // every pointer the launch touches (absent ones are nullptr)
+    int v = std::min(pick_v<native_t>(dy, x, res, inner),
+                     pick_v<native_t>(o, dr, nullptr, inner));
+    // NHWC packs load V fp32 coefficients at once
+    if (L.nhwc && ((uintptr_t)scale % ((size_t)v * sizeof(float))) != 0) v = 1;
+    const int grid = elemt_grid(total, v);
+    MSBN_DISPATCH_V(v, VMAX, [&] {
+      auto launch = [&](auto mask_c, auto res_c, auto resg_c) {
+        constexpr bool MASK_ = decltype(mask_c)::value;
+        constexpr bool RES_ = decltype(res_c)::value;
+        constexpr bool RESG_ = decltype(resg_c)::value;
+        if (!L.nhwc) {
+          hipLaunchKernelGGL(
+              (bn_frozen_bwd_elemt_nchw<native_t, VV, MASK_, RES_, RESG_>),
+              dim3(grid), dim3(MSBN_BLOCK), 0, stream, dy, x, res, o, dr,
+              scale, shift, total, L.C, L.S);
+        } else {
+          hipLaunchKernelGGL(
+              (bn_frozen_bwd_elemt_nhwc<native_t, VV, MASK_, RES_, RESG_>),
+              dim3(grid), dim3(MSBN_BLOCK), 0, stream, dy, x, res, o, dr,
+              scale, shift, total, L.C);
+        }
+      };
+      using T = std::true_type;
+      using F = std::false_type;
+      if (!relu_mask) launch(F{}, F{}, F{});
+      else if (has_res && resg) launch(T{}, T{}, T{});
+      else if (has_res) launch(T{}, T{}, F{});
+      else if (resg) launch(T{}, F{}, T{});
+      else launch(T{}, F{}, F{});
+    });
+  });
+  return {dx, dres};
 }
 
 // ---------------------------------------------------------------------------

@@ -101,6 +101,23 @@ batch_norm_backward_reduce_act(
     bool weight_g, bool bias_g, const c10::optional<at::Tensor>& coefs_in,
     const c10::optional<at::Tensor>& gm_out);
 
+// ---- frozen path (normalize with running stats, autograd on) --------------
+// One launch: (running_mean, running_var, eps, weight?, bias?) -> packed fp32
+// [scale(C) | shift(C)], the buffer batch_norm_elemt_act(coefs_in=) consumes.
+at::Tensor bn_frozen_coefs(const at::Tensor& running_mean,
+                           const at::Tensor& running_var, double eps,
+                           const c10::optional<at::Tensor>& weight,
+                           const c10::optional<at::Tensor>& bias);
+
+// dx = scale[c]*g, dres = g with g = grad_out * 1[z > 0] (gate recomputed
+// from input/residual when relu_mask; input is not touched otherwise).
+// Returns (dx-or-undefined, dres-or-undefined); without the gate dres is
+// grad_out itself.
+std::tuple<at::Tensor, at::Tensor> batch_norm_frozen_backward_elemt(
+    const at::Tensor& grad_out, const c10::optional<at::Tensor>& input,
+    const c10::optional<at::Tensor>& residual, const at::Tensor& coefs,
+    bool relu_mask, bool want_input_grad, bool want_res_grad);
+
 // ---- small-plane world-1 fused path (single launch fwd / bwd) -------------
 // Stock K10-style block-per-channel kernels gated to small NCHW planes
 // (GAN / small-per-GPU-batch regime): one kernel does stats + running

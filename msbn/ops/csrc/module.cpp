@@ -62,6 +62,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("relu_mask"), py::arg("want_res_grad"),
         py::arg("coefs") = py::none());
 
+  m.def("bn_frozen_coefs", &msbn::bn_frozen_coefs, py::arg("running_mean"),
+        py::arg("running_var"), py::arg("eps"), py::arg("weight"),
+        py::arg("bias"));
+  m.def("batch_norm_frozen_backward_elemt",
+        &msbn::batch_norm_frozen_backward_elemt, py::arg("grad_out"),
+        py::arg("input"), py::arg("residual"), py::arg("coefs"),
+        py::arg("relu_mask"), py::arg("want_input_grad"),
+        py::arg("want_res_grad"));
+
   m.def("bn_fused_local_eligible", &msbn::bn_fused_local_eligible,
         py::arg("input"), py::arg("weight"), py::arg("bias"),
         py::arg("running_mean"), py::arg("running_var"));
