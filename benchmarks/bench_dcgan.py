@@ -29,6 +29,9 @@ def main():
     p.add_argument("--stock", action="store_true",
                    help="stock torch SyncBatchNorm+DDP comparison line "
                         "(identical architecture and init)")
+    p.add_argument("--no-fused-d", action="store_true",
+                   help="keep the discriminator's BN + LeakyReLU pairs "
+                        "unfused (A/B line for the fused leaky epilogue)")
     p.add_argument("--benchmark", action="store_true",
                    help="MIOpen conv autotune (uses/extends the in-tree "
                         "miopen_db find-db)")
@@ -87,7 +90,10 @@ def main():
             from msbn.nn import fuse_bn_act
 
             G = fuse_bn_act(msbn.convert_sync_batchnorm(msbn.models.Generator())).to(device)
-            D = msbn.convert_sync_batchnorm(msbn.models.Discriminator()).to(device)
+            D = msbn.convert_sync_batchnorm(msbn.models.Discriminator())
+            if not args.no_fused_d:
+                D = fuse_bn_act(D)
+            D = D.to(device)
             if world > 1:
                 G = msbn.parallel.DistributedDataParallel(
                     G, device_ids=[args.local_rank] if use_cuda else None)
@@ -184,7 +190,8 @@ def main():
             "config": {"model": "dcgan64", "per_gpu_batch": bs,
                        "parallelism": f"dp{world}",
                        "hip_graph": graph is not None,
-                       "impl": "stock" if args.stock else "msbn"},
+                       "impl": "stock" if args.stock else "msbn",
+                       "fused_d": not (args.stock or args.no_fused_d)},
         }))
     if world > 1:
         dist.destroy_process_group()

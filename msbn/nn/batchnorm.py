@@ -17,6 +17,7 @@ Differences from stock, by design (documented, not accidental):
     no GPU->CPU sync per layer and safe under hipGraph capture.
 """
 
+import math
 import os
 from typing import Optional
 
@@ -170,12 +171,28 @@ def _momentum_factor(module) -> float:
     return module.momentum
 
 
+def _check_negative_slope(relu: bool, negative_slope) -> float:
+    """Validate a module's (relu, negative_slope) pair; returns the slope."""
+    negative_slope = float(negative_slope)
+    if not math.isfinite(negative_slope):
+        raise ValueError(
+            f"negative_slope must be finite (got {negative_slope})"
+        )
+    if negative_slope != 0.0 and not relu:
+        raise ValueError(
+            "negative_slope is the slope of the fused activation: it needs "
+            "relu=True"
+        )
+    return negative_slope
+
+
 def _composed_running_stats_forward(
     input: Tensor, residual: Optional[Tensor], weight, bias, running_mean,
-    running_var, eps: float, relu: bool,
+    running_var, eps: float, relu: bool, negative_slope: float = 0.0,
 ) -> Tensor:
-    """Differentiable eager expression of relu?(bn_running(x) [+ residual]):
-    the CPU path, and the GPU A/B baseline under MSBN_FROZEN_COMPOSED=1."""
+    """Differentiable eager expression of act?(bn_running(x) [+ residual]),
+    act = ReLU or LeakyReLU(negative_slope): the CPU path, and the GPU A/B
+    baseline under MSBN_FROZEN_COMPOSED=1."""
     rm = running_mean.to(torch.float32)
     rv = running_var.to(torch.float32)
     invstd = torch.rsqrt(rv + eps)
@@ -193,14 +210,19 @@ def _composed_running_stats_forward(
     if residual is not None:
         out = out + residual.to(torch.float32)
     if relu:
-        out = torch.relu(out)
+        if negative_slope == 0.0:
+            out = torch.relu(out)
+        else:
+            out = torch.nn.functional.leaky_relu(out, negative_slope)
     return out.to(input.dtype)
 
 
 def _running_stats_forward(
-    module, input: Tensor, residual: Optional[Tensor], relu: bool
+    module, input: Tensor, residual: Optional[Tensor], relu: bool,
+    negative_slope: float = 0.0,
 ) -> Tensor:
-    """Normalize with the module's running statistics (eval mode / frozen):
+    """Normalize with the module's running statistics (eval mode / frozen),
+    then the optional fused ReLU / LeakyReLU(negative_slope):
 
       * GPU, autograd on  -> FrozenBatchNormActFunction (coefs kernel + one
         elemt launch forward, one elementwise kernel backward);
@@ -217,18 +239,19 @@ def _running_stats_forward(
         rm = module.running_mean.to(torch.float32)
         invstd = torch.rsqrt(module.running_var.to(torch.float32) + module.eps)
         return _ops.batch_norm_elemt_act(
-            input, residual, module.weight, module.bias, rm, invstd, relu
+            input, residual, module.weight, module.bias, rm, invstd, relu,
+            None, negative_slope,
         )
     if input.is_cuda and not _FROZEN_COMPOSED:
         from msbn.nn.frozen import FrozenBatchNormActFunction
 
         return FrozenBatchNormActFunction.apply(
             input, residual, module.weight, module.bias, module.running_mean,
-            module.running_var, module.eps, relu,
+            module.running_var, module.eps, relu, negative_slope,
         )
     return _composed_running_stats_forward(
         input, residual, module.weight, module.bias, module.running_mean,
-        module.running_var, module.eps, relu,
+        module.running_var, module.eps, relu, negative_slope,
     )
 
 

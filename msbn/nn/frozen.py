@@ -10,6 +10,9 @@ The detection fine-tuning recipe (frozen backbone BN) and any BatchNorm in
             with the ReLU gate recomputed in-kernel.  Without a ReLU the
             kernel never reads x, so the input is not kept alive.
 
+A non-zero ``negative_slope`` turns the ReLU into LeakyReLU (forward
+z>0 ? z : slope*z, gate z>0 ? dy : slope*dy) in the same kernels.
+
 With fixed statistics there are no batch reductions.  Only when the affine
 parameters themselves need a gradient (a trainable BN put in ``.eval()``)
 does backward run the existing per-channel reduce kernel first.
@@ -26,7 +29,8 @@ import torch
 from torch.nn import Module
 
 from msbn import ops
-from msbn.nn.batchnorm import _NormBase, _running_stats_forward
+from msbn.nn.batchnorm import (_NormBase, _check_negative_slope,
+                               _running_stats_forward)
 from msbn.nn.functions import _contig, _match_layout
 
 
@@ -39,18 +43,20 @@ def _dense_format(t: torch.Tensor) -> torch.memory_format:
     return torch.contiguous_format
 
 
-def _elemt(input, residual, coefs, relu: bool):
+def _elemt(input, residual, coefs, relu: bool, negative_slope: float = 0.0):
     C = int(input.shape[1])
     scale, shift = coefs[:C], coefs[C:]
     if input.is_cuda:
         # mean / invstd / weight / bias are not consulted when coefs is given
         return ops.batch_norm_elemt_act(
-            input, residual, None, None, scale, scale, relu, coefs
+            input, residual, None, None, scale, scale, relu, coefs,
+            negative_slope,
         )
     # CPU reference takes (mean, invstd, weight, bias): mean=0, invstd=scale,
     # bias=shift reproduces x*scale + shift
     return ops.batch_norm_elemt_act(
-        input, residual, None, shift, torch.zeros_like(scale), scale, relu
+        input, residual, None, shift, torch.zeros_like(scale), scale, relu,
+        None, negative_slope,
     )
 
 
@@ -71,7 +77,9 @@ class FrozenBatchNormActFunction(torch.autograd.Function):
         running_var: torch.Tensor,
         eps: float,
         relu: bool,
+        negative_slope: float = 0.0,
     ):
+        ctx.negative_slope = negative_slope
         input = _contig(input)
         if residual is not None:
             residual = _match_layout(residual, input)
@@ -106,13 +114,14 @@ class FrozenBatchNormActFunction(torch.autograd.Function):
         ctx.memory_format = _dense_format(input)
         if input.numel() == 0:
             return torch.empty_like(input)
-        return _elemt(input, residual, coefs, relu)
+        return _elemt(input, residual, coefs, relu, negative_slope)
 
     @staticmethod
     def backward(ctx, grad_output: torch.Tensor):
         (coefs, input, residual, weight, bias, running_mean,
          running_var) = ctx.saved_tensors
         relu = ctx.relu
+        slope = ctx.negative_slope
         grad_output = grad_output.contiguous(memory_format=ctx.memory_format) \
             if input is None else _match_layout(grad_output, input)
         need_input_g = ctx.needs_input_grad[0]
@@ -126,7 +135,7 @@ class FrozenBatchNormActFunction(torch.autograd.Function):
                 torch.empty_like(grad_output) if need_res_g else None,
                 torch.zeros_like(weight) if need_weight_g else None,
                 torch.zeros_like(bias) if need_bias_g else None,
-                None, None, None, None,
+                None, None, None, None, None,
             )
 
         grad_weight = grad_bias = None
@@ -142,7 +151,7 @@ class FrozenBatchNormActFunction(torch.autograd.Function):
                 else None
             _, _, grad_weight, grad_bias = ops.batch_norm_backward_reduce_act(
                 grad_output, input, residual, mean, invstd, weight, bias,
-                relu, False, need_weight_g, need_bias_g, coefs, gm,
+                relu, False, need_weight_g, need_bias_g, coefs, gm, slope,
             )
             if gm is not None:
                 grad_output, relu = gm, False
@@ -152,14 +161,14 @@ class FrozenBatchNormActFunction(torch.autograd.Function):
             grad_input, grad_res = ops.batch_norm_frozen_backward_elemt(
                 grad_output, input if relu else None,
                 residual if relu else None, coefs, relu, need_input_g,
-                need_res_g,
+                need_res_g, slope,
             )
         return (
             grad_input,
             grad_res,
             grad_weight if need_weight_g else None,
             grad_bias if need_bias_g else None,
-            None, None, None, None,
+            None, None, None, None, None,
         )
 
 
@@ -167,6 +176,7 @@ class FrozenBatchNorm2d(_NormBase):
     """BatchNorm with fixed statistics AND fixed affine (+ optional fused
     residual-add / ReLU epilogue): ``forward(x, residual=None)`` ==
     ``relu?(bn_eval(x) [+ residual])`` whatever ``.training`` says.
+    ``relu=True, negative_slope=s`` makes the activation LeakyReLU(s).
 
     ``weight``, ``bias``, ``running_mean``, ``running_var`` and
     ``num_batches_tracked`` are buffers (zero parameters) under the same
@@ -178,7 +188,8 @@ class FrozenBatchNorm2d(_NormBase):
     _msbn_frozen = True
 
     def __init__(self, num_features: int, eps: float = 1e-5,
-                 relu: bool = False, device=None, dtype=None) -> None:
+                 relu: bool = False, device=None, dtype=None,
+                 negative_slope: float = 0.0) -> None:
         # buffers instead of _NormBase's parameters: no _NormBase.__init__
         Module.__init__(self)
         factory_kwargs = {"device": device, "dtype": dtype}
@@ -188,6 +199,7 @@ class FrozenBatchNorm2d(_NormBase):
         self.affine = True
         self.track_running_stats = True
         self.relu = relu
+        self.negative_slope = _check_negative_slope(relu, negative_slope)
         self.register_buffer("weight",
                              torch.ones(num_features, **factory_kwargs))
         self.register_buffer("bias",
@@ -213,7 +225,11 @@ class FrozenBatchNorm2d(_NormBase):
             )
 
     def extra_repr(self):
-        return f"{self.num_features}, eps={self.eps}, relu={self.relu}"
+        s = f"{self.num_features}, eps={self.eps}, relu={self.relu}"
+        slope = getattr(self, "negative_slope", 0.0)
+        if slope != 0.0:
+            s += f", negative_slope={slope}"
+        return s
 
     def _load_from_state_dict(
         self, state_dict, prefix, local_metadata, strict,
@@ -232,10 +248,15 @@ class FrozenBatchNorm2d(_NormBase):
     def forward(self, input: torch.Tensor,
                 residual: Optional[torch.Tensor] = None) -> torch.Tensor:
         self._check_input_dim(input)
-        return _running_stats_forward(self, input, residual, self.relu)
+        # default: modules pickled before negative_slope existed
+        return _running_stats_forward(
+            self, input, residual, self.relu,
+            getattr(self, "negative_slope", 0.0),
+        )
 
 
-def _frozen_from(bn, relu: bool) -> FrozenBatchNorm2d:
+def _frozen_from(bn, relu: bool,
+                 negative_slope: float = 0.0) -> FrozenBatchNorm2d:
     """A FrozenBatchNorm2d sharing ``bn``'s tensors."""
     if not bn.track_running_stats or bn.running_mean is None:
         raise ValueError(
@@ -244,7 +265,8 @@ def _frozen_from(bn, relu: bool) -> FrozenBatchNorm2d:
         )
     out = FrozenBatchNorm2d(bn.num_features, bn.eps, relu=relu,
                             device=bn.running_mean.device,
-                            dtype=bn.running_mean.dtype)
+                            dtype=bn.running_mean.dtype,
+                            negative_slope=negative_slope)
     if bn.weight is not None:
         out.weight = bn.weight.detach()
     if bn.bias is not None:
@@ -263,13 +285,17 @@ def freeze_batchnorm(module: Module) -> Module:
     """Recursively replace every BatchNorm (torch.nn BatchNorm1d/2d/3d and
     SyncBatchNorm; msbn BatchNorm*, SyncBatchNorm and SyncBatchNormAct2d)
     with a ``FrozenBatchNorm2d`` that shares its tensors and keeps a fused
-    ReLU epilogue.  ``affine=False`` becomes ones / zeros buffers; a source
+    ReLU / LeakyReLU epilogue.  ``affine=False`` becomes ones / zeros buffers; a source
     without running statistics raises."""
     out = module
     targets = (torch.nn.modules.batchnorm._BatchNorm, _NormBase)
     if isinstance(module, targets) and not isinstance(module,
                                                       FrozenBatchNorm2d):
-        out = _frozen_from(module, bool(getattr(module, "relu", False)))
+        relu = bool(getattr(module, "relu", False))
+        out = _frozen_from(
+            module, relu,
+            getattr(module, "negative_slope", 0.0) if relu else 0.0,
+        )
     for name, child in module.named_children():
         out.add_module(name, freeze_batchnorm(child))
     return out

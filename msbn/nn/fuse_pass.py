@@ -1,10 +1,13 @@
 """fuse_bn_act: graph-free module-tree pass that merges adjacent
-(BatchNorm2d | SyncBatchNorm, ReLU) pairs inside nn.Sequential containers
-into a single SyncBatchNormAct2d (one-kernel epilogue, identical math).
-A (FrozenBatchNorm2d, ReLU) pair becomes a FrozenBatchNorm2d(relu=True).
+(BatchNorm2d | SyncBatchNorm, ReLU | LeakyReLU) pairs inside nn.Sequential
+containers into a single SyncBatchNormAct2d (one-kernel epilogue, identical
+math).  A LeakyReLU's ``negative_slope`` is carried into the fused module;
+``inplace`` is irrelevant for either activation.  A (FrozenBatchNorm2d,
+ReLU | LeakyReLU) pair becomes a FrozenBatchNorm2d(relu=True[,
+negative_slope=s]).
 
-Works on any model whose BN+ReLU pairs live in Sequentials (DCGAN,
-torchvision-style stems, custom CNNs).  Residual-add fusion requires the
+Works on any model whose BN+activation pairs live in Sequentials (DCGAN
+generator and discriminator, torchvision-style stems, custom CNNs).  Residual-add fusion requires the
 block to call the module with ``residual=`` (see msbn.models.resnet's fused
 blocks) and is not attempted here.
 
@@ -18,15 +21,22 @@ from msbn.nn.frozen import FrozenBatchNorm2d, _frozen_from
 from msbn.nn.fused import SyncBatchNormAct2d
 
 
-def _to_act(bn, relu_module):
+_ACTS = (nn.ReLU, nn.LeakyReLU)
+
+
+def _to_act(bn, act_module):
+    relu = isinstance(act_module, _ACTS)
+    slope = (float(act_module.negative_slope)
+             if isinstance(act_module, nn.LeakyReLU) else 0.0)
     if isinstance(bn, FrozenBatchNorm2d):
-        # frozen stays frozen: same tensors, ReLU folded into the epilogue
-        return _frozen_from(bn, relu=isinstance(relu_module, nn.ReLU))
+        # frozen stays frozen: same tensors, activation folded into the
+        # epilogue
+        return _frozen_from(bn, relu=relu, negative_slope=slope)
     out = SyncBatchNormAct2d(
         bn.num_features, bn.eps, bn.momentum, bn.affine,
         bn.track_running_stats,
         getattr(bn, "process_group", None),
-        relu=isinstance(relu_module, nn.ReLU),
+        relu=relu, negative_slope=slope,
     )
     if bn.affine:
         out.weight = bn.weight
@@ -47,7 +57,8 @@ def _fusable_bn(m) -> bool:
 
 
 def fuse_bn_act(module: nn.Module) -> nn.Module:
-    """Recursively fuse (BN, ReLU) pairs inside Sequential containers."""
+    """Recursively fuse (BN, ReLU) and (BN, LeakyReLU) pairs inside
+    Sequential containers."""
     for name, child in module.named_children():
         fuse_bn_act(child)
         if isinstance(child, nn.Sequential):
@@ -59,7 +70,7 @@ def fuse_bn_act(module: nn.Module) -> nn.Module:
                 if (
                     i + 1 < len(items)
                     and _fusable_bn(m)
-                    and isinstance(items[i + 1][1], nn.ReLU)
+                    and isinstance(items[i + 1][1], _ACTS)
                 ):
                     new_items.append((k, _to_act(m, items[i + 1][1])))
                     i += 2

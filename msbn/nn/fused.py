@@ -1,6 +1,8 @@
-"""Fused SyncBatchNorm(+residual add)(+ReLU) — the msbn epilogue-fusion path.
+"""Fused SyncBatchNorm(+residual add)(+ReLU | LeakyReLU) — the msbn
+epilogue-fusion path.
 
-Mathematically identical to ``relu(bn(x) + residual)`` composed from separate
+Mathematically identical to ``relu(bn(x) + residual)`` (or
+``leaky_relu(bn(x) + residual, negative_slope)``) composed from separate
 modules, but executed as ONE elementwise kernel forward and mask-recomputing
 kernels backward (no clamp / add / threshold_backward kernels, no stored mask,
 ~3x fewer full-tensor round trips on the BN backward — see
@@ -17,8 +19,8 @@ import torch
 import torch.distributed as dist
 
 from msbn import ops
-from msbn.nn.batchnorm import (SyncBatchNorm, _momentum_factor,
-                               _running_stats_forward)
+from msbn.nn.batchnorm import (SyncBatchNorm, _check_negative_slope,
+                               _momentum_factor, _running_stats_forward)
 from msbn.nn.functions import (_combined_view, _contig, _force_sync,
                                _match_layout, compute_sync_stats)
 
@@ -38,7 +40,9 @@ class SyncBatchNormActFunction(torch.autograd.Function):
         process_group,
         world_size: int,
         relu: bool,
+        negative_slope: float = 0.0,
     ):
+        ctx.negative_slope = negative_slope
         input = _contig(input)
         if residual is not None:
             residual = _match_layout(residual, input)
@@ -62,7 +66,7 @@ class SyncBatchNormActFunction(torch.autograd.Function):
             # normalize(+res)(+relu) in ONE kernel (K10-family)
             y, mean, invstd, count_sum, coefs = ops.batch_norm_fwd_fused_local(
                 input, residual, weight, bias, eps, momentum,
-                running_mean, running_var, relu,
+                running_mean, running_var, relu, negative_slope,
             )
             ctx.save_for_backward(input, residual, weight, bias, mean,
                                   invstd, count_sum, coefs)
@@ -96,7 +100,8 @@ class SyncBatchNormActFunction(torch.autograd.Function):
         if input.numel() == 0:
             return torch.empty_like(input)
         return ops.batch_norm_elemt_act(
-            input, residual, weight, bias, mean, invstd, relu, coefs
+            input, residual, weight, bias, mean, invstd, relu, coefs,
+            negative_slope,
         )
 
     @staticmethod
@@ -111,6 +116,7 @@ class SyncBatchNormActFunction(torch.autograd.Function):
             coefs = None
         grad_output = _match_layout(grad_output, input)
         relu = ctx.relu
+        slope = ctx.negative_slope
         process_group = ctx.process_group
         world_size = ctx.world_size
         need_input_g = ctx.needs_input_grad[0]
@@ -127,6 +133,7 @@ class SyncBatchNormActFunction(torch.autograd.Function):
                 ops.batch_norm_bwd_fused_local(
                     grad_output, input, residual, mean, invstd, weight,
                     coefs, relu, need_res_g, need_weight_g, need_bias_g,
+                    slope,
                 )
             )
             return (
@@ -134,13 +141,14 @@ class SyncBatchNormActFunction(torch.autograd.Function):
                 grad_res if need_res_g else None,
                 grad_weight if need_weight_g else None,
                 grad_bias if need_bias_g else None,
-                None, None, None, None, None, None, None,
+                None, None, None, None, None, None, None, None,
             )
 
         # Masked-grad materialization: when the residual branch needs its
-        # gradient, the reduce pass writes gm = dy*1[z>0] once; the elemt
-        # pass then reads gm instead of (dy, residual) and gm itself IS the
-        # residual gradient -> one fewer full-tensor read+write (8A -> 7A).
+        # gradient, the reduce pass writes gm = dy*1[z>0] (leaky: slope*dy
+        # where z<=0) once; the elemt pass then reads gm instead of
+        # (dy, residual) and gm itself IS the residual gradient -> one fewer
+        # full-tensor read+write (8A -> 7A).
         use_gm = (
             relu and residual is not None and need_res_g and input.is_cuda
             and input.numel() > 0
@@ -163,13 +171,14 @@ class SyncBatchNormActFunction(torch.autograd.Function):
                 torch.empty_like(grad_output) if need_res_g else None,
                 torch.zeros_like(weight) if need_weight_g else None,
                 torch.zeros_like(bias) if need_bias_g else None,
-                None, None, None, None, None, None, None,
+                None, None, None, None, None, None, None, None,
             )
         gm = torch.empty_like(grad_output) if use_gm else None
         sum_dy, sum_dy_xmu, grad_weight, grad_bias = (
             ops.batch_norm_backward_reduce_act(
                 grad_output, input, residual, mean, invstd, weight, bias,
                 relu, need_input_g, need_weight_g, need_bias_g, coefs, gm,
+                slope,
             )
         )
         grad_input = grad_res = None
@@ -196,13 +205,14 @@ class SyncBatchNormActFunction(torch.autograd.Function):
                 grad_input, grad_res = ops.batch_norm_backward_elemt_act(
                     grad_output, input, residual, mean, invstd, weight, bias,
                     sum_dy, sum_dy_xmu, count_sum, relu, need_res_g, coefs,
+                    slope,
                 )
         return (
             grad_input if need_input_g else None,
             grad_res,
             grad_weight if need_weight_g else None,
             grad_bias if need_bias_g else None,
-            None, None, None, None, None, None, None,
+            None, None, None, None, None, None, None, None,
         )
 
 
@@ -210,19 +220,32 @@ class SyncBatchNormAct2d(SyncBatchNorm):
     """SyncBatchNorm with a fused (optional residual-add +) ReLU epilogue.
 
     forward(x, residual=None) == relu(bn(x) + residual) with identical math.
+    ``relu=True, negative_slope=s`` makes the activation LeakyReLU(s):
+    leaky_relu(bn(x) + residual, s).  The slope is a hyper-parameter, not
+    state: state-dict keys are those of SyncBatchNorm.
     """
 
     def __init__(self, num_features, eps=1e-5, momentum=0.1, affine=True,
                  track_running_stats=True, process_group=None, device=None,
-                 dtype=None, relu: bool = True):
+                 dtype=None, relu: bool = True, negative_slope: float = 0.0):
         super().__init__(num_features, eps, momentum, affine,
                          track_running_stats, process_group, device, dtype)
         self.relu = relu
+        self.negative_slope = _check_negative_slope(relu, negative_slope)
+
+    def extra_repr(self):
+        s = super().extra_repr()
+        slope = getattr(self, "negative_slope", 0.0)
+        if slope != 0.0:
+            s += f", negative_slope={slope}"
+        return s
 
     def forward(self, input: torch.Tensor,
                 residual: Optional[torch.Tensor] = None) -> torch.Tensor:
         self._check_input_dim(input)
         self._check_non_zero_input_channels(input)
+        # default: modules pickled before negative_slope existed
+        slope = getattr(self, "negative_slope", 0.0)
 
         bn_training = self.training or (
             self.running_mean is None and self.running_var is None
@@ -235,7 +258,8 @@ class SyncBatchNormAct2d(SyncBatchNorm):
         )
 
         if not bn_training:
-            return _running_stats_forward(self, input, residual, self.relu)
+            return _running_stats_forward(self, input, residual, self.relu,
+                                          slope)
 
         process_group = None
         world_size = 1
@@ -247,5 +271,5 @@ class SyncBatchNormAct2d(SyncBatchNorm):
         running_var = self.running_var if self.track_running_stats else None
         return SyncBatchNormActFunction.apply(
             input, residual, self.weight, self.bias, running_mean, running_var,
-            self.eps, factor, process_group, world_size, self.relu,
+            self.eps, factor, process_group, world_size, self.relu, slope,
         )

@@ -184,22 +184,24 @@ def bn_fused_local_eligible(input, weight, bias, running_mean, running_var):
 
 
 def batch_norm_fwd_fused_local(input, residual, weight, bias, eps, momentum,
-                               running_mean, running_var, relu):
-    """ONE kernel: local stats + running update + normalize(+res)(+relu).
+                               running_mean, running_var, relu,
+                               negative_slope: float = 0.0):
+    """ONE kernel: local stats + running update + normalize(+res)(+relu,
+    or LeakyReLU for a non-zero ``negative_slope``).
     Returns (y, mean, invstd, count[1], coefs[2C])."""
     return _require_hip().batch_norm_fwd_fused_local(
         input, residual, weight, bias, eps, momentum, running_mean,
-        running_var, relu,
+        running_var, relu, negative_slope,
     )
 
 
 def batch_norm_bwd_fused_local(grad_out, input, residual, mean, invstd,
                                weight, coefs, relu_mask, want_res_grad,
-                               weight_g, bias_g):
+                               weight_g, bias_g, negative_slope: float = 0.0):
     """ONE kernel: whole local BN backward (reduce + coefs + dx(+dres))."""
     return _require_hip().batch_norm_bwd_fused_local(
         grad_out, input, residual, mean, invstd, weight, coefs, relu_mask,
-        want_res_grad, weight_g, bias_g,
+        want_res_grad, weight_g, bias_g, negative_slope,
     )
 
 
@@ -211,42 +213,48 @@ def bn_make_coefs(mean, invstd, weight, bias):
 
 
 def batch_norm_elemt_act(input, residual, weight, bias, mean, invstd,
-                         relu: bool, coefs=None):
+                         relu: bool, coefs=None, negative_slope: float = 0.0):
+    """y = act(x*scale + shift [+ residual]); ``relu`` turns the activation
+    on and ``negative_slope`` (only consulted then) makes it a LeakyReLU."""
     if input.is_cuda:
         return _require_hip().batch_norm_elemt_act(
-            input, residual, weight, bias, mean, invstd, relu, coefs
+            input, residual, weight, bias, mean, invstd, relu, coefs,
+            negative_slope,
         )
     return _ref.batch_norm_elemt_act(
-        input, residual, weight, bias, mean, invstd, relu
+        input, residual, weight, bias, mean, invstd, relu, negative_slope
     )
 
 
 def batch_norm_backward_reduce_act(grad_out, input, residual, mean, invstd,
                                    weight, bias, relu_mask, input_g, weight_g,
-                                   bias_g, coefs=None, gm_out=None):
+                                   bias_g, coefs=None, gm_out=None,
+                                   negative_slope: float = 0.0):
     if input.is_cuda:
         return _require_hip().batch_norm_backward_reduce_act(
             grad_out, input, residual, mean, invstd, weight, bias, relu_mask,
-            input_g, weight_g, bias_g, coefs, gm_out,
+            input_g, weight_g, bias_g, coefs, gm_out, negative_slope,
         )
     return _ref.batch_norm_backward_reduce_act(
         grad_out, input, residual, mean, invstd, weight, bias, relu_mask,
-        input_g, weight_g, bias_g, gm_out,
+        input_g, weight_g, bias_g, gm_out, negative_slope,
     )
 
 
 def batch_norm_backward_elemt_act(grad_out, input, residual, mean, invstd,
                                   weight, bias, sum_dy, sum_dy_xmu, count,
-                                  relu_mask, want_res_grad, coefs=None):
+                                  relu_mask, want_res_grad, coefs=None,
+                                  negative_slope: float = 0.0):
     if input.is_cuda:
         dx, dres = _require_hip().batch_norm_backward_elemt_act(
             grad_out, input, residual, mean, invstd, weight, bias, sum_dy,
             sum_dy_xmu, count, relu_mask, want_res_grad, coefs,
+            negative_slope,
         )
         return dx, (dres if want_res_grad else None)
     return _ref.batch_norm_backward_elemt_act(
         grad_out, input, residual, mean, invstd, weight, bias, sum_dy,
-        sum_dy_xmu, count, relu_mask, want_res_grad,
+        sum_dy_xmu, count, relu_mask, want_res_grad, negative_slope,
     )
 
 
@@ -264,21 +272,23 @@ def bn_frozen_coefs(running_mean, running_var, eps: float, weight, bias):
 
 def batch_norm_frozen_backward_elemt(grad_out, input, residual, coefs,
                                      relu_mask: bool, want_input_grad: bool,
-                                     want_res_grad: bool):
+                                     want_res_grad: bool,
+                                     negative_slope: float = 0.0):
     """Backward of the frozen BN(+add)(+ReLU) epilogue, one elementwise pass:
-    dx = scale*g, dres = g, g = grad_out*1[z>0].  ``input`` / ``residual``
-    are only needed for the gate (``relu_mask``); without it ``dres`` is
-    ``grad_out`` itself.  Returns (dx-or-None, dres-or-None)."""
+    dx = scale*g, dres = g, g = grad_out*1[z>0] (LeakyReLU for a non-zero
+    ``negative_slope``: g = negative_slope*grad_out where z <= 0).  ``input``
+    / ``residual`` are only needed for the gate (``relu_mask``); without it
+    ``dres`` is ``grad_out`` itself.  Returns (dx-or-None, dres-or-None)."""
     if grad_out.is_cuda:
         dx, dres = _require_hip().batch_norm_frozen_backward_elemt(
             grad_out, input, residual, coefs, relu_mask, want_input_grad,
-            want_res_grad,
+            want_res_grad, negative_slope,
         )
         return (dx if want_input_grad else None,
                 dres if want_res_grad else None)
     return _ref.batch_norm_frozen_backward_elemt(
         grad_out, input, residual, coefs, relu_mask, want_input_grad,
-        want_res_grad,
+        want_res_grad, negative_slope,
     )
 
 

@@ -140,9 +140,11 @@ def _act_coefs(mean, invstd, weight, bias):
 
 
 def batch_norm_elemt_act(
-    input, residual, weight, bias, mean, invstd, relu: bool
+    input, residual, weight, bias, mean, invstd, relu: bool,
+    negative_slope: float = 0.0,
 ):
-    """y = relu?(x*scale + shift [+ residual]) — fused epilogue reference."""
+    """y = act?(x*scale + shift [+ residual]) — fused epilogue reference.
+    ``negative_slope`` (consulted only with ``relu``) selects LeakyReLU."""
     scale, shift = _act_coefs(mean, invstd, weight, bias)
     z = input.to(torch.float32) * _chan_view(scale, input) + _chan_view(
         shift, input
@@ -150,12 +152,22 @@ def batch_norm_elemt_act(
     if residual is not None:
         z = z + residual.to(torch.float32)
     if relu:
-        z = torch.relu(z)
+        if negative_slope == 0.0:
+            z = torch.relu(z)
+        else:
+            z = torch.where(z > 0, z, negative_slope * z)
     return z.to(input.dtype)
 
 
+def _gate(z, g, negative_slope: float):
+    """g through the activation's gate; z == 0 takes the negative branch."""
+    if negative_slope == 0.0:
+        return torch.where(z > 0, g, torch.zeros_like(g))
+    return torch.where(z > 0, g, negative_slope * g)
+
+
 def _masked_grad(grad_out, input, residual, mean, invstd, weight, bias,
-                 relu_mask: bool):
+                 relu_mask: bool, negative_slope: float = 0.0):
     g = grad_out.to(torch.float32)
     if relu_mask:
         scale, shift = _act_coefs(mean, invstd, weight, bias)
@@ -164,16 +176,16 @@ def _masked_grad(grad_out, input, residual, mean, invstd, weight, bias,
         )
         if residual is not None:
             z = z + residual.to(torch.float32)
-        g = torch.where(z > 0, g, torch.zeros_like(g))
+        g = _gate(z, g, negative_slope)
     return g
 
 
 def batch_norm_backward_reduce_act(
     grad_out, input, residual, mean, invstd, weight, bias, relu_mask,
-    input_g, weight_g, bias_g, gm_out=None,
+    input_g, weight_g, bias_g, gm_out=None, negative_slope: float = 0.0,
 ):
     g = _masked_grad(grad_out, input, residual, mean, invstd, weight, bias,
-                     relu_mask)
+                     relu_mask, negative_slope)
     if gm_out is not None:
         gm_out.copy_(g.to(grad_out.dtype))
     return batch_norm_backward_reduce(
@@ -183,10 +195,10 @@ def batch_norm_backward_reduce_act(
 
 def batch_norm_backward_elemt_act(
     grad_out, input, residual, mean, invstd, weight, bias, sum_dy,
-    sum_dy_xmu, count, relu_mask, want_res_grad,
+    sum_dy_xmu, count, relu_mask, want_res_grad, negative_slope: float = 0.0,
 ):
     g = _masked_grad(grad_out, input, residual, mean, invstd, weight, bias,
-                     relu_mask)
+                     relu_mask, negative_slope)
     dx = batch_norm_backward_elemt(
         g, input, mean, invstd, weight, sum_dy, sum_dy_xmu, count
     )
@@ -204,11 +216,12 @@ def bn_frozen_coefs(running_mean, running_var, eps: float, weight, bias):
 
 def batch_norm_frozen_backward_elemt(
     grad_out, input, residual, coefs, relu_mask: bool,
-    want_input_grad: bool, want_res_grad: bool,
+    want_input_grad: bool, want_res_grad: bool, negative_slope: float = 0.0,
 ):
-    """Backward of y = relu?(x*scale + shift [+ residual]) with FIXED scale /
-    shift: dx = scale*g, dres = g, g = grad_out * 1[z > 0].  ``input`` and
-    ``residual`` are only consulted for the gate (relu_mask)."""
+    """Backward of y = act?(x*scale + shift [+ residual]) with FIXED scale /
+    shift: dx = scale*g, dres = g, g = grad_out * 1[z > 0] (or
+    negative_slope*grad_out where z <= 0).  ``input`` and ``residual`` are
+    only consulted for the gate (relu_mask)."""
     C = grad_out.shape[1]
     scale = _chan_view(coefs[:C], grad_out)
     g = grad_out.to(torch.float32)
@@ -216,7 +229,7 @@ def batch_norm_frozen_backward_elemt(
         z = input.to(torch.float32) * scale + _chan_view(coefs[C:], grad_out)
         if residual is not None:
             z = z + residual.to(torch.float32)
-        g = torch.where(z > 0, g, torch.zeros_like(g))
+        g = _gate(z, g, negative_slope)
     dx = (g * scale).to(grad_out.dtype) if want_input_grad else None
     dres = None
     if want_res_grad:

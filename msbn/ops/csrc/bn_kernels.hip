@@ -342,16 +342,18 @@ __global__ void bn_affine_bwd(const float* __restrict__ mean,
 
 // =====================================================================
 // elementwise: y = act(x*scale[c] + shift[c] [+ res])
-// RELU / RES are compile-time: the fused BN(+add)+ReLU epilogue replaces the
-// eager clamp / add kernels and their full-tensor round trips (guide G13:
-// fuse into the producing kernel).
+// ACT / RES are compile-time: the fused BN(+add)+ReLU/LeakyReLU epilogue
+// replaces the eager clamp / add kernels and their full-tensor round trips
+// (guide G13: fuse into the producing kernel).  ACT is kActNone / kActRelu /
+// kActLeaky (common.hpp); `slope` is only read by the kActLeaky
+// instantiations, so none / relu keep their arithmetic.
 // =====================================================================
-template <typename T, int V, bool RELU, bool RES>
+template <typename T, int V, int ACT, bool RES>
 __global__ void bn_elemt_nchw(const T* __restrict__ x,
                               const T* __restrict__ res, T* __restrict__ y,
                               const float* __restrict__ scale,
                               const float* __restrict__ shift, int64_t total,
-                              int64_t C, int64_t S) {
+                              int64_t C, int64_t S, float slope) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
        i * V < total; i += stride) {
@@ -361,7 +363,7 @@ __global__ void bn_elemt_nchw(const T* __restrict__ x,
     if (V == 1) {
       float z = to_f(nt_load1(&x[e])) * sc + sh;
       if (RES) z += to_f(nt_load1(&res[e]));
-      if (RELU) z = fmaxf(z, 0.f);
+      z = act_fwd<ACT>(z, slope);
       nt_store1(&y[e], from_f<T>(z));
     } else {
       Pack<T, V> px = nt_load<T, V>(&x[e]);
@@ -372,7 +374,7 @@ __global__ void bn_elemt_nchw(const T* __restrict__ x,
       for (int k = 0; k < V; ++k) {
         float z = to_f(px.v[k]) * sc + sh;
         if (RES) z += to_f(pr.v[k]);
-        if (RELU) z = fmaxf(z, 0.f);
+        z = act_fwd<ACT>(z, slope);
         py.v[k] = from_f<T>(z);
       }
       nt_store<T, V>(&y[e], py);
@@ -380,12 +382,12 @@ __global__ void bn_elemt_nchw(const T* __restrict__ x,
   }
 }
 
-template <typename T, int V, bool RELU, bool RES>
+template <typename T, int V, int ACT, bool RES>
 __global__ void bn_elemt_nhwc(const T* __restrict__ x,
                               const T* __restrict__ res, T* __restrict__ y,
                               const float* __restrict__ scale,
                               const float* __restrict__ shift, int64_t total,
-                              int64_t C) {
+                              int64_t C, float slope) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
        i * V < total; i += stride) {
@@ -394,7 +396,7 @@ __global__ void bn_elemt_nhwc(const T* __restrict__ x,
     if (V == 1) {
       float z = to_f(nt_load1(&x[e])) * scale[c] + shift[c];
       if (RES) z += to_f(nt_load1(&res[e]));
-      if (RELU) z = fmaxf(z, 0.f);
+      z = act_fwd<ACT>(z, slope);
       nt_store1(&y[e], from_f<T>(z));
     } else {
       Pack<T, V> px = nt_load<T, V>(&x[e]);
@@ -407,7 +409,7 @@ __global__ void bn_elemt_nhwc(const T* __restrict__ x,
       for (int k = 0; k < V; ++k) {
         float z = to_f(px.v[k]) * ps.v[k] + pb.v[k];
         if (RES) z += to_f(pr.v[k]);
-        if (RELU) z = fmaxf(z, 0.f);
+        z = act_fwd<ACT>(z, slope);
         py.v[k] = from_f<T>(z);
       }
       nt_store<T, V>(&y[e], py);
@@ -417,11 +419,12 @@ __global__ void bn_elemt_nhwc(const T* __restrict__ x,
 
 // =====================================================================
 // backward reduce partial: {sum_g, sum_g*(x-mean)} per channel, where
-// g = dy masked by the fused-ReLU gate when MASK: the pre-activation
+// g = dy through the fused activation's gate when ACT (relu: z>0 ? dy : 0,
+// leaky: z>0 ? dy : slope*dy): the pre-activation
 // z = scale[c]*x + shift[c] (+ res) is recomputed in-kernel, so the fused
 // forward never has to store a mask or the pre-activation tensor.
 // =====================================================================
-template <typename T, int V, bool MASK, bool RES, bool GMOUT>
+template <typename T, int V, int ACT, bool RES, bool GMOUT>
 __global__ void bn_bwd_reduce_partial_nchw(const T* __restrict__ dy,
                                            const T* __restrict__ x,
                                            const T* __restrict__ res,
@@ -431,11 +434,11 @@ __global__ void bn_bwd_reduce_partial_nchw(const T* __restrict__ dy,
                                            const float* __restrict__ shift,
                                            double* __restrict__ ws, int64_t N,
                                            int64_t C, int64_t S, int64_t chunkN,
-                                           int64_t chunkS) {
+                                           int64_t chunkS, float slope) {
   const int64_t c = blockIdx.x;
   const float m = mean[c];
-  const float sc = MASK ? scale[c] : 0.f;
-  const float sh = MASK ? shift[c] : 0.f;
+  const float sc = ACT ? scale[c] : 0.f;
+  const float sh = ACT ? shift[c] : 0.f;
   const int64_t n0 = blockIdx.y * chunkN;
   const int64_t n1 = i64min(n0 + chunkN, N);
   const int64_t s0 = blockIdx.z * chunkS;
@@ -448,10 +451,10 @@ __global__ void bn_bwd_reduce_partial_nchw(const T* __restrict__ dy,
       for (int64_t s = s0 + threadIdx.x; s < s1; s += blockDim.x) {
         float g = to_f(nt_load1(&dy[base + s]));
         const float xv = to_f(nt_load1(&x[base + s]));
-        if (MASK) {
+        if (ACT) {
           float z = sc * xv + sh;
           if (RES) z += to_f(nt_load1(&res[base + s]));
-          if (z <= 0.f) g = 0.f;
+          g = act_gate<ACT>(z, g, slope);
         }
         if (GMOUT) nt_store1(&gm_out[base + s], from_f<T>(g));
         acc.add2(g, g * (xv - m));
@@ -471,10 +474,10 @@ __global__ void bn_bwd_reduce_partial_nchw(const T* __restrict__ dy,
         for (int k = 0; k < V; ++k) {
           float g = to_f(pg.v[k]);
           const float xv = to_f(px.v[k]);
-          if (MASK) {
+          if (ACT) {
             float z = sc * xv + sh;
             if (RES) z += to_f(pr.v[k]);
-            if (z <= 0.f) g = 0.f;
+            g = act_gate<ACT>(z, g, slope);
           }
           if (GMOUT) pm.v[k] = from_f<T>(g);
           acc.add2(g, g * (xv - m));
@@ -499,18 +502,18 @@ __global__ void bn_bwd_reduce_partial_nchw(const T* __restrict__ dy,
   }
 }
 
-template <typename T, bool MASK, bool RES, bool GMOUT>
+template <typename T, int ACT, bool RES, bool GMOUT>
 __global__ void bn_bwd_reduce_partial_nchw_flat(
     const T* __restrict__ dy, const T* __restrict__ x,
     const T* __restrict__ res, T* __restrict__ gm_out,
     const float* __restrict__ mean,
     const float* __restrict__ scale, const float* __restrict__ shift,
     double* __restrict__ ws, int64_t N, int64_t C, int64_t S,
-    int64_t chunk_len) {
+    int64_t chunk_len, float slope) {
   const int64_t c = blockIdx.x;
   const float m = mean[c];
-  const float sc = MASK ? scale[c] : 0.f;
-  const float sh = MASK ? shift[c] : 0.f;
+  const float sc = ACT ? scale[c] : 0.f;
+  const float sh = ACT ? shift[c] : 0.f;
   const int64_t NS = N * S;
   const int64_t p0 = (int64_t)blockIdx.y * chunk_len;
   const int64_t p1 = i64min(p0 + chunk_len, NS);
@@ -521,10 +524,10 @@ __global__ void bn_bwd_reduce_partial_nchw_flat(
     const int64_t e = (n * C + c) * S + s;
     float g = to_f(nt_load1(&dy[e]));
     const float xv = to_f(nt_load1(&x[e]));
-    if (MASK) {
+    if (ACT) {
       float z = sc * xv + sh;
       if (RES) z += to_f(nt_load1(&res[e]));
-      if (z <= 0.f) g = 0.f;
+      g = act_gate<ACT>(z, g, slope);
     }
     if (GMOUT) nt_store1(&gm_out[e], from_f<T>(g));
     acc.add2(g, g * (xv - m));
@@ -544,7 +547,7 @@ __global__ void bn_bwd_reduce_partial_nchw_flat(
   }
 }
 
-template <typename T, int V, bool MASK, bool RES, bool GMOUT>
+template <typename T, int V, int ACT, bool RES, bool GMOUT>
 __global__ void bn_bwd_reduce_partial_nhwc(const T* __restrict__ dy,
                                            const T* __restrict__ x,
                                            const T* __restrict__ res,
@@ -554,7 +557,8 @@ __global__ void bn_bwd_reduce_partial_nhwc(const T* __restrict__ dy,
                                            const float* __restrict__ shift,
                                            double* __restrict__ ws,
                                            int64_t rows, int64_t C,
-                                           int64_t chunk_rows, int lpr) {
+                                           int64_t chunk_rows, int lpr,
+                                           float slope) {
   const int rpi = blockDim.x / lpr;
   const int lane = threadIdx.x % lpr;
   const int rowoff = threadIdx.x / lpr;
@@ -570,7 +574,7 @@ __global__ void bn_bwd_reduce_partial_nhwc(const T* __restrict__ dy,
 #pragma unroll
     for (int k = 0; k < V; ++k) {
       m[k] = mean[c + k];
-      if (MASK) {
+      if (ACT) {
         scv[k] = scale[c + k];
         shv[k] = shift[c + k];
       }
@@ -587,10 +591,10 @@ __global__ void bn_bwd_reduce_partial_nhwc(const T* __restrict__ dy,
       for (int k = 0; k < V; ++k) {
         float g = to_f(pg.v[k]);
         const float xv = to_f(px.v[k]);
-        if (MASK) {
+        if (ACT) {
           float z = scv[k] * xv + shv[k];
           if (RES) z += to_f(pr.v[k]);
-          if (z <= 0.f) g = 0.f;
+          g = act_gate<ACT>(z, g, slope);
         }
         if (GMOUT) pm.v[k] = from_f<T>(g);
         acc[k].add2(g, g * (xv - m[k]));
@@ -672,11 +676,12 @@ __global__ void bn_bwd_reduce_finalize(const double* __restrict__ ws,
 }
 
 // =====================================================================
-// backward elementwise: dx = a[c]*g + b[c]*x + d[c], with the fused-ReLU
-// gate recomputed in-kernel when MASK (g = z>0 ? dy : 0); RESG additionally
-// writes the residual-branch gradient dres = g (the add node's pass-through).
+// backward elementwise: dx = a[c]*g + b[c]*x + d[c], with the activation
+// gate recomputed in-kernel when ACT (g = z>0 ? dy : 0 or slope*dy); RESG
+// additionally writes the residual-branch gradient dres = g (the add node's
+// pass-through).
 // =====================================================================
-template <typename T, int V, bool MASK, bool RES, bool RESG>
+template <typename T, int V, int ACT, bool RES, bool RESG>
 __global__ void bn_bwd_elemt_nchw(const T* __restrict__ dy,
                                   const T* __restrict__ x,
                                   const T* __restrict__ res,
@@ -686,22 +691,23 @@ __global__ void bn_bwd_elemt_nchw(const T* __restrict__ dy,
                                   const float* __restrict__ cd,
                                   const float* __restrict__ scale,
                                   const float* __restrict__ shift,
-                                  int64_t total, int64_t C, int64_t S) {
+                                  int64_t total, int64_t C, int64_t S,
+                                  float slope) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
        i * V < total; i += stride) {
     const int64_t e = i * V;
     const int64_t c = (e / S) % C;
     const float A = ca[c], B = cb[c], D = cd[c];
-    const float sc = MASK ? scale[c] : 0.f;
-    const float sh = MASK ? shift[c] : 0.f;
+    const float sc = ACT ? scale[c] : 0.f;
+    const float sh = ACT ? shift[c] : 0.f;
     if (V == 1) {
       float g = to_f(nt_load1(&dy[e]));
       const float xv = to_f(nt_load1(&x[e]));
-      if (MASK) {
+      if (ACT) {
         float z = sc * xv + sh;
         if (RES) z += to_f(nt_load1(&res[e]));
-        if (z <= 0.f) g = 0.f;
+        g = act_gate<ACT>(z, g, slope);
       }
       nt_store1(&dx[e], from_f<T>(A * g + B * xv + D));
       if (RESG) nt_store1(&dres[e], from_f<T>(g));
@@ -715,10 +721,10 @@ __global__ void bn_bwd_elemt_nchw(const T* __restrict__ dy,
       for (int k = 0; k < V; ++k) {
         float g = to_f(pg.v[k]);
         const float xv = to_f(px.v[k]);
-        if (MASK) {
+        if (ACT) {
           float z = sc * xv + sh;
           if (RES) z += to_f(pr.v[k]);
-          if (z <= 0.f) g = 0.f;
+          g = act_gate<ACT>(z, g, slope);
         }
         po.v[k] = from_f<T>(A * g + B * xv + D);
         if (RESG) pq.v[k] = from_f<T>(g);
@@ -729,7 +735,7 @@ __global__ void bn_bwd_elemt_nchw(const T* __restrict__ dy,
   }
 }
 
-template <typename T, int V, bool MASK, bool RES, bool RESG>
+template <typename T, int V, int ACT, bool RES, bool RESG>
 __global__ void bn_bwd_elemt_nhwc(const T* __restrict__ dy,
                                   const T* __restrict__ x,
                                   const T* __restrict__ res,
@@ -739,7 +745,7 @@ __global__ void bn_bwd_elemt_nhwc(const T* __restrict__ dy,
                                   const float* __restrict__ cd,
                                   const float* __restrict__ scale,
                                   const float* __restrict__ shift,
-                                  int64_t total, int64_t C) {
+                                  int64_t total, int64_t C, float slope) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
        i * V < total; i += stride) {
@@ -748,10 +754,10 @@ __global__ void bn_bwd_elemt_nhwc(const T* __restrict__ dy,
     if (V == 1) {
       float g = to_f(nt_load1(&dy[e]));
       const float xv = to_f(nt_load1(&x[e]));
-      if (MASK) {
+      if (ACT) {
         float z = scale[c] * xv + shift[c];
         if (RES) z += to_f(nt_load1(&res[e]));
-        if (z <= 0.f) g = 0.f;
+        g = act_gate<ACT>(z, g, slope);
       }
       nt_store1(&dx[e], from_f<T>(ca[c] * g + cb[c] * xv + cd[c]));
       if (RESG) nt_store1(&dres[e], from_f<T>(g));
@@ -762,7 +768,7 @@ __global__ void bn_bwd_elemt_nhwc(const T* __restrict__ dy,
       Pack<float, V> pb = *reinterpret_cast<const Pack<float, V>*>(&cb[c]);
       Pack<float, V> pd = *reinterpret_cast<const Pack<float, V>*>(&cd[c]);
       Pack<float, V> psc, psh;
-      if (MASK) {
+      if (ACT) {
         psc = *reinterpret_cast<const Pack<float, V>*>(&scale[c]);
         psh = *reinterpret_cast<const Pack<float, V>*>(&shift[c]);
       }
@@ -773,10 +779,10 @@ __global__ void bn_bwd_elemt_nhwc(const T* __restrict__ dy,
       for (int k = 0; k < V; ++k) {
         float g = to_f(pg.v[k]);
         const float xv = to_f(px.v[k]);
-        if (MASK) {
+        if (ACT) {
           float z = psc.v[k] * xv + psh.v[k];
           if (RES) z += to_f(pr.v[k]);
-          if (z <= 0.f) g = 0.f;
+          g = act_gate<ACT>(z, g, slope);
         }
         po.v[k] = from_f<T>(pa.v[k] * g + pb.v[k] * xv + pd.v[k]);
         if (RESG) pq.v[k] = from_f<T>(g);
@@ -792,10 +798,10 @@ __global__ void bn_bwd_elemt_nhwc(const T* __restrict__ dy,
 // batch reduction anywhere.  One tiny kernel folds (running_mean,
 // running_var, eps, weight, bias) into the packed [scale | shift] buffer the
 // forward elemt kernels consume; backward is ONE elementwise pass
-//   dx = scale[c]*g,  dres = g,  g = dy * 1[z > 0]
-// with the ReLU gate recomputed from (x, scale, shift[, res]) exactly as
-// bn_bwd_elemt_* does.  Without the gate (!MASK) x is never read, so the
-// layer does not have to keep its input alive.
+//   dx = scale[c]*g,  dres = g,  g = dy * 1[z > 0]  (leaky: slope*dy else)
+// with the activation gate recomputed from (x, scale, shift[, res]) exactly
+// as bn_bwd_elemt_* does.  Without the gate (kActNone) x is never read, so
+// the layer does not have to keep its input alive.
 // =====================================================================
 template <typename RT, typename WT>
 __global__ void bn_frozen_coefs(const RT* __restrict__ rmean,
@@ -812,10 +818,10 @@ __global__ void bn_frozen_coefs(const RT* __restrict__ rmean,
   shift[c] = -to_f(rmean[c]) * sc + (b != nullptr ? to_f(b[c]) : 0.f);
 }
 
-// x / res are only dereferenced when MASK (the host passes nullptr
+// x / res are only dereferenced when ACT (the host passes nullptr
 // otherwise); dx may be nullptr when only the residual branch needs its
 // gradient (wave-uniform branch).
-template <typename T, int V, bool MASK, bool RES, bool RESG>
+template <typename T, int V, int ACT, bool RES, bool RESG>
 __global__ void bn_frozen_bwd_elemt_nchw(const T* __restrict__ dy,
                                          const T* __restrict__ x,
                                          const T* __restrict__ res,
@@ -823,36 +829,37 @@ __global__ void bn_frozen_bwd_elemt_nchw(const T* __restrict__ dy,
                                          T* __restrict__ dres,
                                          const float* __restrict__ scale,
                                          const float* __restrict__ shift,
-                                         int64_t total, int64_t C, int64_t S) {
+                                         int64_t total, int64_t C, int64_t S,
+                                         float slope) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
        i * V < total; i += stride) {
     const int64_t e = i * V;
     const int64_t c = (e / S) % C;
     const float sc = scale[c];
-    const float sh = MASK ? shift[c] : 0.f;
+    const float sh = ACT ? shift[c] : 0.f;
     if (V == 1) {
       float g = to_f(nt_load1(&dy[e]));
-      if (MASK) {
+      if (ACT) {
         float z = sc * to_f(nt_load1(&x[e])) + sh;
         if (RES) z += to_f(nt_load1(&res[e]));
-        if (z <= 0.f) g = 0.f;
+        g = act_gate<ACT>(z, g, slope);
       }
       if (dx != nullptr) nt_store1(&dx[e], from_f<T>(sc * g));
       if (RESG) nt_store1(&dres[e], from_f<T>(g));
     } else {
       Pack<T, V> pg = nt_load<T, V>(&dy[e]);
       Pack<T, V> px, pr;
-      if (MASK) px = nt_load<T, V>(&x[e]);
-      if (MASK && RES) pr = nt_load<T, V>(&res[e]);
+      if (ACT) px = nt_load<T, V>(&x[e]);
+      if (ACT && RES) pr = nt_load<T, V>(&res[e]);
       Pack<T, V> po, pq;
 #pragma unroll
       for (int k = 0; k < V; ++k) {
         float g = to_f(pg.v[k]);
-        if (MASK) {
+        if (ACT) {
           float z = sc * to_f(px.v[k]) + sh;
           if (RES) z += to_f(pr.v[k]);
-          if (z <= 0.f) g = 0.f;
+          g = act_gate<ACT>(z, g, slope);
         }
         po.v[k] = from_f<T>(sc * g);
         if (RESG) pq.v[k] = from_f<T>(g);
@@ -863,7 +870,7 @@ __global__ void bn_frozen_bwd_elemt_nchw(const T* __restrict__ dy,
   }
 }
 
-template <typename T, int V, bool MASK, bool RES, bool RESG>
+template <typename T, int V, int ACT, bool RES, bool RESG>
 __global__ void bn_frozen_bwd_elemt_nhwc(const T* __restrict__ dy,
                                          const T* __restrict__ x,
                                          const T* __restrict__ res,
@@ -871,7 +878,8 @@ __global__ void bn_frozen_bwd_elemt_nhwc(const T* __restrict__ dy,
                                          T* __restrict__ dres,
                                          const float* __restrict__ scale,
                                          const float* __restrict__ shift,
-                                         int64_t total, int64_t C) {
+                                         int64_t total, int64_t C,
+                                         float slope) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
        i * V < total; i += stride) {
@@ -880,10 +888,10 @@ __global__ void bn_frozen_bwd_elemt_nhwc(const T* __restrict__ dy,
     if (V == 1) {
       float g = to_f(nt_load1(&dy[e]));
       const float sc = scale[c];
-      if (MASK) {
+      if (ACT) {
         float z = sc * to_f(nt_load1(&x[e])) + shift[c];
         if (RES) z += to_f(nt_load1(&res[e]));
-        if (z <= 0.f) g = 0.f;
+        g = act_gate<ACT>(z, g, slope);
       }
       if (dx != nullptr) nt_store1(&dx[e], from_f<T>(sc * g));
       if (RESG) nt_store1(&dres[e], from_f<T>(g));
@@ -892,19 +900,19 @@ __global__ void bn_frozen_bwd_elemt_nhwc(const T* __restrict__ dy,
       Pack<float, V> psc = *reinterpret_cast<const Pack<float, V>*>(&scale[c]);
       Pack<float, V> psh;
       Pack<T, V> px, pr;
-      if (MASK) {
+      if (ACT) {
         psh = *reinterpret_cast<const Pack<float, V>*>(&shift[c]);
         px = nt_load<T, V>(&x[e]);
       }
-      if (MASK && RES) pr = nt_load<T, V>(&res[e]);
+      if (ACT && RES) pr = nt_load<T, V>(&res[e]);
       Pack<T, V> po, pq;
 #pragma unroll
       for (int k = 0; k < V; ++k) {
         float g = to_f(pg.v[k]);
-        if (MASK) {
+        if (ACT) {
           float z = psc.v[k] * to_f(px.v[k]) + psh.v[k];
           if (RES) z += to_f(pr.v[k]);
-          if (z <= 0.f) g = 0.f;
+          g = act_gate<ACT>(z, g, slope);
         }
         po.v[k] = from_f<T>(psc.v[k] * g);
         if (RESG) pq.v[k] = from_f<T>(g);
@@ -927,7 +935,7 @@ __global__ void bn_frozen_bwd_elemt_nhwc(const T* __restrict__ dy,
 // V-wide flat indexing: pack pp covers elements [pp*V, pp*V+V) of the
 // channel plane; S % V == 0 (host-gated) keeps every pack inside one row.
 // int32 arithmetic throughout (plane <= 32K elems by gate).
-template <typename T, int V, bool RELU, bool RES>
+template <typename T, int V, int ACT, bool RES>
 __global__ void bn_fwd_fused_small_nchw(
     const T* __restrict__ x, const T* __restrict__ res, T* __restrict__ y,
     int N, int64_t C, int S, float eps, float momentum,
@@ -935,7 +943,7 @@ __global__ void bn_fwd_fused_small_nchw(
     float* __restrict__ count_out, float* __restrict__ rmean,
     float* __restrict__ rvar, const float* __restrict__ w,
     const float* __restrict__ b, float* __restrict__ scale_out,
-    float* __restrict__ shift_out) {
+    float* __restrict__ shift_out, float slope) {
   const int64_t c = blockIdx.x;
   const int plane = N * S;
   const int packs = plane / V;
@@ -989,27 +997,27 @@ __global__ void bn_fwd_fused_small_nchw(
     for (int k = 0; k < V; ++k) {
       float z = to_f(px.v[k]) * sc + sh;
       if (RES) z += to_f(pr.v[k]);
-      if (RELU) z = fmaxf(z, 0.f);
+      z = act_fwd<ACT>(z, slope);
       py.v[k] = from_f<T>(z);
     }
     *reinterpret_cast<Pack<T, V>*>(&y[base]) = py;
   }
 }
 
-template <typename T, int V, bool MASK, bool RES, bool RESG>
+template <typename T, int V, int ACT, bool RES, bool RESG>
 __global__ void bn_bwd_fused_small_nchw(
     const T* __restrict__ dy, const T* __restrict__ x,
     const T* __restrict__ res, T* __restrict__ dx, T* __restrict__ dres,
     const float* __restrict__ mean, const float* __restrict__ invstd,
     const float* __restrict__ scale, const float* __restrict__ shift,
     const float* __restrict__ w, float* __restrict__ gw,
-    float* __restrict__ gb, int N, int64_t C, int S) {
+    float* __restrict__ gb, int N, int64_t C, int S, float slope) {
   const int64_t c = blockIdx.x;
   const int plane = N * S;
   const int packs = plane / V;
   const float m = mean[c];
-  const float sc = MASK ? scale[c] : 0.f;
-  const float sh = MASK ? shift[c] : 0.f;
+  const float sc = ACT ? scale[c] : 0.f;
+  const float sh = ACT ? shift[c] : 0.f;
   double a = 0.0, bb = 0.0;
   for (int pp = threadIdx.x; pp < packs; pp += blockDim.x) {
     const int e = pp * V;
@@ -1018,15 +1026,15 @@ __global__ void bn_bwd_fused_small_nchw(
     Pack<T, V> pg = *reinterpret_cast<const Pack<T, V>*>(&dy[base]);
     Pack<T, V> px = *reinterpret_cast<const Pack<T, V>*>(&x[base]);
     Pack<T, V> pr;
-    if (MASK && RES) pr = *reinterpret_cast<const Pack<T, V>*>(&res[base]);
+    if (ACT && RES) pr = *reinterpret_cast<const Pack<T, V>*>(&res[base]);
 #pragma unroll
     for (int k = 0; k < V; ++k) {
       float g = to_f(pg.v[k]);
       const float xv = to_f(px.v[k]);
-      if (MASK) {
+      if (ACT) {
         float z = sc * xv + sh;
         if (RES) z += to_f(pr.v[k]);
-        if (z <= 0.f) g = 0.f;
+        g = act_gate<ACT>(z, g, slope);
       }
       a += g;
       bb += (double)g * (xv - m);
@@ -1056,15 +1064,15 @@ __global__ void bn_bwd_fused_small_nchw(
     Pack<T, V> pg = *reinterpret_cast<const Pack<T, V>*>(&dy[base]);
     Pack<T, V> px = *reinterpret_cast<const Pack<T, V>*>(&x[base]);
     Pack<T, V> pr, po, pq;
-    if (MASK && RES) pr = *reinterpret_cast<const Pack<T, V>*>(&res[base]);
+    if (ACT && RES) pr = *reinterpret_cast<const Pack<T, V>*>(&res[base]);
 #pragma unroll
     for (int k = 0; k < V; ++k) {
       float g = to_f(pg.v[k]);
       const float xv = to_f(px.v[k]);
-      if (MASK) {
+      if (ACT) {
         float z = sc * xv + sh;
         if (RES) z += to_f(pr.v[k]);
-        if (z <= 0.f) g = 0.f;
+        g = act_gate<ACT>(z, g, slope);
       }
       po.v[k] = from_f<T>(A * g + B * xv + D);
       if (RESG) pq.v[k] = from_f<T>(g);
@@ -1592,6 +1600,36 @@ at::Tensor make_fwd_coefs(const at::Tensor& mean, const at::Tensor& invstd,
       return __VA_ARGS__();                                                  \
     }                                                                        \
   }()
+
+// Activation mode of the fused epilogue: off -> kActNone; on with a zero
+// slope -> kActRelu (the instantiation ReLU models have always run, so their
+// results do not move); any other slope -> kActLeaky.
+inline int act_mode(bool on, float slope) {
+  return !on ? kActNone : (slope == 0.f ? kActRelu : kActLeaky);
+}
+
+#define MSBN_DISPATCH_ACT(MODE, NAME, ...)                                   \
+  [&] {                                                                      \
+    switch (MODE) {                                                          \
+      case kActRelu: {                                                       \
+        constexpr int NAME = kActRelu;                                       \
+        return __VA_ARGS__();                                                \
+      }                                                                      \
+      case kActLeaky: {                                                      \
+        constexpr int NAME = kActLeaky;                                      \
+        return __VA_ARGS__();                                                \
+      }                                                                      \
+      default: {                                                             \
+        constexpr int NAME = kActNone;                                       \
+        return __VA_ARGS__();                                                \
+      }                                                                      \
+    }                                                                        \
+  }()
+
+// The frozen / small-plane launchers prune flag combinations that cannot
+// occur (no gate -> no residual read); they pass the mode as a type.
+template <int ACT>
+using ActC = std::integral_constant<int, ACT>;
 }  // namespace
 
 at::Tensor bn_make_coefs(const at::Tensor& mean, const at::Tensor& invstd,
@@ -1606,10 +1644,13 @@ at::Tensor batch_norm_elemt_act(const at::Tensor& input,
                                 const c10::optional<at::Tensor>& bias,
                                 const at::Tensor& mean,
                                 const at::Tensor& invstd, bool relu,
-                                const c10::optional<at::Tensor>& coefs_in) {
+                                const c10::optional<at::Tensor>& coefs_in,
+                                double negative_slope) {
   const Layout L = get_layout(input);
   auto out = at::empty_like(input);
   if (input.numel() == 0) return out;
+  const float slope = (float)negative_slope;
+  const int act = act_mode(relu, slope);
   auto stream = cur_stream();
   auto coefs = coefs_in.has_value()
                    ? *coefs_in
@@ -1637,16 +1678,16 @@ at::Tensor batch_norm_elemt_act(const at::Tensor& input,
     const int v = pick_v<native_t>(x, y, res, inner);
     const int grid = elemt_grid(total, v);
     MSBN_DISPATCH_V(v, VMAX, [&] {
-      MSBN_DISPATCH_BOOL(relu, RELU_, [&] {
+      MSBN_DISPATCH_ACT(act, ACT_, [&] {
         MSBN_DISPATCH_BOOL(has_res, RES_, [&] {
           if (!L.nhwc) {
-            hipLaunchKernelGGL((bn_elemt_nchw<native_t, VV, RELU_, RES_>),
+            hipLaunchKernelGGL((bn_elemt_nchw<native_t, VV, ACT_, RES_>),
                                dim3(grid), dim3(MSBN_BLOCK), 0, stream, x, res,
-                               y, scale, shift, total, L.C, L.S);
+                               y, scale, shift, total, L.C, L.S, slope);
           } else {
-            hipLaunchKernelGGL((bn_elemt_nhwc<native_t, VV, RELU_, RES_>),
+            hipLaunchKernelGGL((bn_elemt_nhwc<native_t, VV, ACT_, RES_>),
                                dim3(grid), dim3(MSBN_BLOCK), 0, stream, x, res,
-                               y, scale, shift, total, L.C);
+                               y, scale, shift, total, L.C, slope);
           }
         });
       });
@@ -1662,7 +1703,7 @@ at::Tensor batch_norm_elemt(const at::Tensor& input,
                             double eps) {
   (void)eps;  // invstd already folds eps
   return batch_norm_elemt_act(input, c10::nullopt, weight, bias, mean, invstd,
-                              false, c10::nullopt);
+                              false, c10::nullopt, 0.0);
 }
 
 std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor>
@@ -1672,8 +1713,10 @@ batch_norm_backward_reduce_act(
     const at::Tensor& invstd, const c10::optional<at::Tensor>& weight,
     const c10::optional<at::Tensor>& bias, bool relu_mask, bool input_g,
     bool weight_g, bool bias_g, const c10::optional<at::Tensor>& coefs_in,
-    const c10::optional<at::Tensor>& gm_out) {
+    const c10::optional<at::Tensor>& gm_out, double negative_slope) {
   const Layout L = get_layout(input);
+  const float slope = (float)negative_slope;
+  const int act = act_mode(relu_mask, slope);
   if (input.numel() == 0) {
     auto z32 = input.options().dtype(at::kFloat);
     auto combined0 = at::zeros({2 * L.C}, z32);
@@ -1737,7 +1780,7 @@ batch_norm_backward_reduce_act(
     constexpr int VMAX = 16 / (int)sizeof(native_t);
     at::Tensor ws;
     int nchunks = 0;
-    MSBN_DISPATCH_BOOL(relu_mask, MASK_, [&] {
+    MSBN_DISPATCH_ACT(act, ACT_, [&] {
       MSBN_DISPATCH_BOOL(has_res, RES_, [&] {
         MSBN_DISPATCH_BOOL(want_gm, GM_, [&] {
         if (!L.nhwc) {
@@ -1748,10 +1791,10 @@ batch_norm_backward_reduce_act(
             ws = at::empty({(int64_t)nchunks * L.C * 2},
                            input.options().dtype(at::kDouble));
             hipLaunchKernelGGL(
-                (bn_bwd_reduce_partial_nchw_flat<native_t, MASK_, RES_, GM_>),
+                (bn_bwd_reduce_partial_nchw_flat<native_t, ACT_, RES_, GM_>),
                 g.grid, dim3(MSBN_BLOCK), 0, stream, dy, x, res, gm,
                 mean.data_ptr<float>(), scale, shift, ws.data_ptr<double>(),
-                L.N, L.C, L.S, g.chunk_len);
+                L.N, L.C, L.S, g.chunk_len, slope);
           } else {
             auto g = nchw_grid(L.N, L.C, L.S, v);
             nchunks = g.nchunks;
@@ -1759,10 +1802,10 @@ batch_norm_backward_reduce_act(
                            input.options().dtype(at::kDouble));
             MSBN_DISPATCH_V(v, VMAX, [&] {
               hipLaunchKernelGGL(
-                  (bn_bwd_reduce_partial_nchw<native_t, VV, MASK_, RES_, GM_>),
+                  (bn_bwd_reduce_partial_nchw<native_t, VV, ACT_, RES_, GM_>),
                   g.grid, dim3(MSBN_BLOCK), 0, stream, dy, x, res, gm,
                   mean.data_ptr<float>(), scale, shift, ws.data_ptr<double>(),
-                  L.N, L.C, L.S, g.chunkN, g.chunkS);
+                  L.N, L.C, L.S, g.chunkN, g.chunkS, slope);
             });
           }
         } else {
@@ -1773,10 +1816,10 @@ batch_norm_backward_reduce_act(
                          input.options().dtype(at::kDouble));
           MSBN_DISPATCH_V(v, VMAX, [&] {
             hipLaunchKernelGGL(
-                (bn_bwd_reduce_partial_nhwc<native_t, VV, MASK_, RES_, GM_>),
+                (bn_bwd_reduce_partial_nhwc<native_t, VV, ACT_, RES_, GM_>),
                 g.grid, dim3(MSBN_BLOCK), 0, stream, dy, x, res, gm,
                 mean.data_ptr<float>(), scale, shift, ws.data_ptr<double>(),
-                L.rows, L.C, g.chunk_rows, g.lpr);
+                L.rows, L.C, g.chunk_rows, g.lpr, slope);
           });
         }
         });
@@ -1807,7 +1850,7 @@ batch_norm_backward_reduce(const at::Tensor& grad_out, const at::Tensor& input,
   return batch_norm_backward_reduce_act(grad_out, input, c10::nullopt, mean,
                                         invstd, weight, c10::nullopt, false,
                                         input_g, weight_g, bias_g,
-                                        c10::nullopt, c10::nullopt);
+                                        c10::nullopt, c10::nullopt, 0.0);
 }
 
 std::tuple<at::Tensor, at::Tensor> batch_norm_backward_elemt_act(
@@ -1816,8 +1859,11 @@ std::tuple<at::Tensor, at::Tensor> batch_norm_backward_elemt_act(
     const at::Tensor& invstd, const c10::optional<at::Tensor>& weight,
     const c10::optional<at::Tensor>& bias, const at::Tensor& sum_dy,
     const at::Tensor& sum_dy_xmu, const at::Tensor& count, bool relu_mask,
-    bool want_res_grad, const c10::optional<at::Tensor>& coefs_in) {
+    bool want_res_grad, const c10::optional<at::Tensor>& coefs_in,
+    double negative_slope) {
   const Layout L = get_layout(input);
+  const float slope = (float)negative_slope;
+  const int act = act_mode(relu_mask, slope);
   auto dx = at::empty_like(grad_out);
   at::Tensor dres;
   if (want_res_grad) dres = at::empty_like(grad_out);
@@ -1879,19 +1925,19 @@ std::tuple<at::Tensor, at::Tensor> batch_norm_backward_elemt_act(
     const int v = pick_v<native_t>(x, dy, o, inner);
     const int grid = elemt_grid(total, v);
     MSBN_DISPATCH_V(v, VMAX, [&] {
-      MSBN_DISPATCH_BOOL(relu_mask, MASK_, [&] {
+      MSBN_DISPATCH_ACT(act, ACT_, [&] {
         MSBN_DISPATCH_BOOL(has_res, RES_, [&] {
           MSBN_DISPATCH_BOOL(want_res_grad, RESG_, [&] {
             if (!L.nhwc) {
               hipLaunchKernelGGL(
-                  (bn_bwd_elemt_nchw<native_t, VV, MASK_, RES_, RESG_>),
+                  (bn_bwd_elemt_nchw<native_t, VV, ACT_, RES_, RESG_>),
                   dim3(grid), dim3(MSBN_BLOCK), 0, stream, dy, x, res, o, dr,
-                  ca, cb, cd, scale, shift, total, L.C, L.S);
+                  ca, cb, cd, scale, shift, total, L.C, L.S, slope);
             } else {
               hipLaunchKernelGGL(
-                  (bn_bwd_elemt_nhwc<native_t, VV, MASK_, RES_, RESG_>),
+                  (bn_bwd_elemt_nhwc<native_t, VV, ACT_, RES_, RESG_>),
                   dim3(grid), dim3(MSBN_BLOCK), 0, stream, dy, x, res, o, dr,
-                  ca, cb, cd, scale, shift, total, L.C);
+                  ca, cb, cd, scale, shift, total, L.C, slope);
             }
           });
         });
@@ -1908,7 +1954,7 @@ at::Tensor batch_norm_backward_elemt(
     const at::Tensor& count) {
   return std::get<0>(batch_norm_backward_elemt_act(
       grad_out, input, c10::nullopt, mean, invstd, weight, c10::nullopt,
-      sum_dy, sum_dy_xmu, count, false, false, c10::nullopt));
+      sum_dy, sum_dy_xmu, count, false, false, c10::nullopt, 0.0));
 }
 
 // ---------------------------------------------------------------------------
@@ -1964,7 +2010,9 @@ at::Tensor bn_frozen_coefs(const at::Tensor& running_mean,
 std::tuple<at::Tensor, at::Tensor> batch_norm_frozen_backward_elemt(
     const at::Tensor& grad_out, const c10::optional<at::Tensor>& input,
     const c10::optional<at::Tensor>& residual, const at::Tensor& coefs,
-    bool relu_mask, bool want_input_grad, bool want_res_grad) {
+    bool relu_mask, bool want_input_grad, bool want_res_grad,
+    double negative_slope) {
+  const float slope = (float)negative_slope;
   TORCH_CHECK(grad_out.dim() >= 2,
               "batch_norm_frozen_backward_elemt: grad_out must be >= 2-D");
   const Layout L = get_layout(grad_out);
@@ -2027,29 +2075,33 @@ std::tuple<at::Tensor, at::Tensor> batch_norm_frozen_backward_elemt(
     if (L.nhwc && ((uintptr_t)scale % ((size_t)v * sizeof(float))) != 0) v = 1;
     const int grid = elemt_grid(total, v);
     MSBN_DISPATCH_V(v, VMAX, [&] {
-      auto launch = [&](auto mask_c, auto res_c, auto resg_c) {
-        constexpr bool MASK_ = decltype(mask_c)::value;
+      auto launch = [&](auto act_c, auto res_c, auto resg_c) {
+        constexpr int ACT_ = decltype(act_c)::value;
         constexpr bool RES_ = decltype(res_c)::value;
         constexpr bool RESG_ = decltype(resg_c)::value;
         if (!L.nhwc) {
           hipLaunchKernelGGL(
-              (bn_frozen_bwd_elemt_nchw<native_t, VV, MASK_, RES_, RESG_>),
+              (bn_frozen_bwd_elemt_nchw<native_t, VV, ACT_, RES_, RESG_>),
               dim3(grid), dim3(MSBN_BLOCK), 0, stream, dy, x, res, o, dr,
-              scale, shift, total, L.C, L.S);
+              scale, shift, total, L.C, L.S, slope);
         } else {
           hipLaunchKernelGGL(
-              (bn_frozen_bwd_elemt_nhwc<native_t, VV, MASK_, RES_, RESG_>),
+              (bn_frozen_bwd_elemt_nhwc<native_t, VV, ACT_, RES_, RESG_>),
               dim3(grid), dim3(MSBN_BLOCK), 0, stream, dy, x, res, o, dr,
-              scale, shift, total, L.C);
+              scale, shift, total, L.C, slope);
         }
       };
       using T = std::true_type;
       using F = std::false_type;
-      if (!relu_mask) launch(F{}, F{}, F{});
-      else if (has_res && resg) launch(T{}, T{}, T{});
-      else if (has_res) launch(T{}, T{}, F{});
-      else if (resg) launch(T{}, F{}, T{});
-      else launch(T{}, F{}, F{});
+      auto gated = [&](auto act_c) {
+        if (has_res && resg) launch(act_c, T{}, T{});
+        else if (has_res) launch(act_c, T{}, F{});
+        else if (resg) launch(act_c, F{}, T{});
+        else launch(act_c, F{}, F{});
+      };
+      if (!relu_mask) launch(ActC<kActNone>{}, F{}, F{});
+      else if (slope == 0.f) gated(ActC<kActRelu>{});
+      else gated(ActC<kActLeaky>{});
     });
   });
   return {dx, dres};
@@ -2106,7 +2158,8 @@ batch_norm_fwd_fused_local(const at::Tensor& input,
                            double momentum,
                            const c10::optional<at::Tensor>& running_mean,
                            const c10::optional<at::Tensor>& running_var,
-                           bool relu) {
+                           bool relu, double negative_slope) {
+  const float slope = (float)negative_slope;
   const int64_t C = input.size(1);
   const int64_t N = input.size(0);
   const int64_t S = input.numel() / std::max<int64_t>(N * C, 1);
@@ -2144,21 +2197,16 @@ batch_norm_fwd_fused_local(const at::Tensor& input,
     constexpr int VMAX = 16 / (int)sizeof(native_t);
     const int v = pick_v<native_t>(x, res, yp, S);
     MSBN_DISPATCH_V(v, VMAX, [&] {
-      auto launch = [&](auto relu_c, auto res_c) {
-        hipLaunchKernelGGL(
-            (bn_fwd_fused_small_nchw<native_t, VV, decltype(relu_c)::value,
-                                     decltype(res_c)::value>),
-            dim3((unsigned)C), dim3(MSBN_BLOCK), 0, stream, x, res, yp,
-            (int)N, C, (int)S, (float)eps, (float)momentum,
-            mean.data_ptr<float>(), invstd.data_ptr<float>(),
-            count.data_ptr<float>(), rm, rv, w, b, scale_p, shift_p);
-      };
-      using T = std::true_type;
-      using F = std::false_type;
-      if (relu && has_res) launch(T{}, T{});
-      else if (relu) launch(T{}, F{});
-      else if (has_res) launch(F{}, T{});
-      else launch(F{}, F{});
+      MSBN_DISPATCH_ACT(act_mode(relu, slope), ACT_, [&] {
+        MSBN_DISPATCH_BOOL(has_res, RES_, [&] {
+          hipLaunchKernelGGL(
+              (bn_fwd_fused_small_nchw<native_t, VV, ACT_, RES_>),
+              dim3((unsigned)C), dim3(MSBN_BLOCK), 0, stream, x, res, yp,
+              (int)N, C, (int)S, (float)eps, (float)momentum,
+              mean.data_ptr<float>(), invstd.data_ptr<float>(),
+              count.data_ptr<float>(), rm, rv, w, b, scale_p, shift_p, slope);
+        });
+      });
     });
   });
   return {y, mean, invstd, count, coefs};
@@ -2171,7 +2219,8 @@ batch_norm_bwd_fused_local(const at::Tensor& grad_out, const at::Tensor& input,
                            const c10::optional<at::Tensor>& weight,
                            const c10::optional<at::Tensor>& coefs,
                            bool relu_mask, bool want_res_grad, bool weight_g,
-                           bool bias_g) {
+                           bool bias_g, double negative_slope) {
+  const float slope = (float)negative_slope;
   const int64_t C = input.size(1);
   const int64_t N = input.size(0);
   const int64_t S = input.numel() / std::max<int64_t>(N * C, 1);
@@ -2213,25 +2262,33 @@ batch_norm_bwd_fused_local(const at::Tensor& grad_out, const at::Tensor& input,
     const int v1 = pick_v<native_t>(dxp, drp, nullptr, S);
     const int v = std::min(v0, v1);
     MSBN_DISPATCH_V(v, VMAX, [&] {
-      auto launch = [&](auto mask_c, auto res_c, auto resg_c) {
+      auto launch = [&](auto act_c, auto res_c, auto resg_c) {
         hipLaunchKernelGGL(
-            (bn_bwd_fused_small_nchw<native_t, VV, decltype(mask_c)::value,
+            (bn_bwd_fused_small_nchw<native_t, VV, decltype(act_c)::value,
                                      decltype(res_c)::value,
                                      decltype(resg_c)::value>),
             dim3((unsigned)C), dim3(MSBN_BLOCK), 0, stream, dy, x, res, dxp,
             drp, mean.data_ptr<float>(), invstd.data_ptr<float>(), scale_p,
             shift_p, w, weight_g ? gw.data_ptr<float>() : nullptr,
-            bias_g ? gb.data_ptr<float>() : nullptr, (int)N, C, (int)S);
+            bias_g ? gb.data_ptr<float>() : nullptr, (int)N, C, (int)S,
+            slope);
       };
       using T = std::true_type;
       using F = std::false_type;
-      const bool mres = relu_mask && has_res;
-      if (relu_mask && mres && want_res_grad) launch(T{}, T{}, T{});
-      else if (relu_mask && mres) launch(T{}, T{}, F{});
-      else if (relu_mask && want_res_grad) launch(T{}, F{}, T{});
-      else if (relu_mask) launch(T{}, F{}, F{});
-      else if (want_res_grad) launch(F{}, F{}, T{});
-      else launch(F{}, F{}, F{});
+      auto gated = [&](auto act_c) {
+        if (has_res && want_res_grad) launch(act_c, T{}, T{});
+        else if (has_res) launch(act_c, T{}, F{});
+        else if (want_res_grad) launch(act_c, F{}, T{});
+        else launch(act_c, F{}, F{});
+      };
+      if (!relu_mask) {
+        if (want_res_grad) launch(ActC<kActNone>{}, F{}, T{});
+        else launch(ActC<kActNone>{}, F{}, F{});
+      } else if (slope == 0.f) {
+        gated(ActC<kActRelu>{});
+      } else {
+        gated(ActC<kActLeaky>{});
+      }
     });
   });
   return {dx, gw, gb, dres};

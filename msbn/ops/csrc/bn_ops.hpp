@@ -80,6 +80,9 @@ at::Tensor batch_norm_backward_elemt(
 // round trips.
 // coefs = packed [scale(C) | shift(C)] fp32 (bn_make_coefs); pass it to the
 // act ops to avoid recomputing the per-channel affine in each of them.
+// negative_slope generalises the activation to LeakyReLU: forward
+// z>0 ? z : slope*z, gate z>0 ? dy : slope*dy.  It is only consulted when
+// the relu / relu_mask flag is set, and 0.0 runs the plain ReLU kernels.
 at::Tensor bn_make_coefs(const at::Tensor& mean, const at::Tensor& invstd,
                          const c10::optional<at::Tensor>& weight,
                          const c10::optional<at::Tensor>& bias);
@@ -90,7 +93,8 @@ at::Tensor batch_norm_elemt_act(const at::Tensor& input,
                                 const c10::optional<at::Tensor>& bias,
                                 const at::Tensor& mean,
                                 const at::Tensor& invstd, bool relu,
-                                const c10::optional<at::Tensor>& coefs_in);
+                                const c10::optional<at::Tensor>& coefs_in,
+                                double negative_slope);
 
 std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor>
 batch_norm_backward_reduce_act(
@@ -99,7 +103,7 @@ batch_norm_backward_reduce_act(
     const at::Tensor& invstd, const c10::optional<at::Tensor>& weight,
     const c10::optional<at::Tensor>& bias, bool relu_mask, bool input_g,
     bool weight_g, bool bias_g, const c10::optional<at::Tensor>& coefs_in,
-    const c10::optional<at::Tensor>& gm_out);
+    const c10::optional<at::Tensor>& gm_out, double negative_slope);
 
 // ---- frozen path (normalize with running stats, autograd on) --------------
 // One launch: (running_mean, running_var, eps, weight?, bias?) -> packed fp32
@@ -109,14 +113,17 @@ at::Tensor bn_frozen_coefs(const at::Tensor& running_mean,
                            const c10::optional<at::Tensor>& weight,
                            const c10::optional<at::Tensor>& bias);
 
-// dx = scale[c]*g, dres = g with g = grad_out * 1[z > 0] (gate recomputed
-// from input/residual when relu_mask; input is not touched otherwise).
+// dx = scale[c]*g, dres = g with g = grad_out * 1[z > 0], or for a non-zero
+// negative_slope g = z > 0 ? grad_out : negative_slope*grad_out (gate
+// recomputed from input/residual when relu_mask; input is not touched
+// otherwise).
 // Returns (dx-or-undefined, dres-or-undefined); without the gate dres is
 // grad_out itself.
 std::tuple<at::Tensor, at::Tensor> batch_norm_frozen_backward_elemt(
     const at::Tensor& grad_out, const c10::optional<at::Tensor>& input,
     const c10::optional<at::Tensor>& residual, const at::Tensor& coefs,
-    bool relu_mask, bool want_input_grad, bool want_res_grad);
+    bool relu_mask, bool want_input_grad, bool want_res_grad,
+    double negative_slope);
 
 // ---- small-plane world-1 fused path (single launch fwd / bwd) -------------
 // Stock K10-style block-per-channel kernels gated to small NCHW planes
@@ -137,7 +144,7 @@ batch_norm_fwd_fused_local(const at::Tensor& input,
                            double momentum,
                            const c10::optional<at::Tensor>& running_mean,
                            const c10::optional<at::Tensor>& running_var,
-                           bool relu);
+                           bool relu, double negative_slope);
 
 // returns (dx, grad_weight?, grad_bias?, dres?)
 std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor>
@@ -147,7 +154,7 @@ batch_norm_bwd_fused_local(const at::Tensor& grad_out, const at::Tensor& input,
                            const c10::optional<at::Tensor>& weight,
                            const c10::optional<at::Tensor>& coefs,
                            bool relu_mask, bool want_res_grad, bool weight_g,
-                           bool bias_g);
+                           bool bias_g, double negative_slope);
 
 // returns (grad_input, grad_residual-or-undefined)
 std::tuple<at::Tensor, at::Tensor> batch_norm_backward_elemt_act(
@@ -156,6 +163,7 @@ std::tuple<at::Tensor, at::Tensor> batch_norm_backward_elemt_act(
     const at::Tensor& invstd, const c10::optional<at::Tensor>& weight,
     const c10::optional<at::Tensor>& bias, const at::Tensor& sum_dy,
     const at::Tensor& sum_dy_xmu, const at::Tensor& count, bool relu_mask,
-    bool want_res_grad, const c10::optional<at::Tensor>& coefs_in);
+    bool want_res_grad, const c10::optional<at::Tensor>& coefs_in,
+    double negative_slope);
 
 }  // namespace msbn

@@ -45,6 +45,33 @@ __device__ __forceinline__ __half from_f<__half>(float x) {
   return __float2half(x);
 }
 
+// --------------------------------------------------- fused epilogue activation
+// Compile-time activation mode of the fused BN(+add)+act epilogue.  kActNone
+// is 0 so kernels can test `if (ACT)` for "there is a gate to recompute".
+// The leaky slope is a runtime kernel argument, consulted by kActLeaky only.
+constexpr int kActNone = 0;
+constexpr int kActRelu = 1;
+constexpr int kActLeaky = 2;
+
+// forward: y = act(z)
+template <int ACT>
+__device__ __forceinline__ float act_fwd(float z, float slope) {
+  if (ACT == kActRelu) return fmaxf(z, 0.f);
+  if (ACT == kActLeaky) return z > 0.f ? z : slope * z;
+  return z;
+}
+
+// backward: g = dy * act'(z); z == 0 takes the negative branch in both modes
+// (stock threshold_backward / leaky_relu_backward convention).
+template <int ACT>
+__device__ __forceinline__ float act_gate(float z, float g, float slope) {
+  if (ACT == kActRelu) {
+    if (z <= 0.f) g = 0.f;
+  }
+  if (ACT == kActLeaky) g = z > 0.f ? g : slope * g;
+  return g;
+}
+
 // ------------------------------------------------ nontemporal pack load/store
 // Streaming tensors (activations / gradients: read or written exactly once
 // per launch and far larger than L2) use nontemporal accesses — the nt cache

@@ -47,20 +47,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("batch_norm_elemt_act", &msbn::batch_norm_elemt_act, py::arg("input"),
         py::arg("residual"), py::arg("weight"), py::arg("bias"),
         py::arg("mean"), py::arg("invstd"), py::arg("relu"),
-        py::arg("coefs") = py::none());
+        py::arg("coefs") = py::none(), py::arg("negative_slope") = 0.0);
   m.def("batch_norm_backward_reduce_act",
         &msbn::batch_norm_backward_reduce_act, py::arg("grad_out"),
         py::arg("input"), py::arg("residual"), py::arg("mean"),
         py::arg("invstd"), py::arg("weight"), py::arg("bias"),
         py::arg("relu_mask"), py::arg("input_g"), py::arg("weight_g"),
         py::arg("bias_g"), py::arg("coefs") = py::none(),
-        py::arg("gm_out") = py::none());
+        py::arg("gm_out") = py::none(), py::arg("negative_slope") = 0.0);
   m.def("batch_norm_backward_elemt_act", &msbn::batch_norm_backward_elemt_act,
         py::arg("grad_out"), py::arg("input"), py::arg("residual"),
         py::arg("mean"), py::arg("invstd"), py::arg("weight"), py::arg("bias"),
         py::arg("sum_dy"), py::arg("sum_dy_xmu"), py::arg("count"),
         py::arg("relu_mask"), py::arg("want_res_grad"),
-        py::arg("coefs") = py::none());
+        py::arg("coefs") = py::none(), py::arg("negative_slope") = 0.0);
 
   m.def("bn_frozen_coefs", &msbn::bn_frozen_coefs, py::arg("running_mean"),
         py::arg("running_var"), py::arg("eps"), py::arg("weight"),
@@ -69,7 +69,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         &msbn::batch_norm_frozen_backward_elemt, py::arg("grad_out"),
         py::arg("input"), py::arg("residual"), py::arg("coefs"),
         py::arg("relu_mask"), py::arg("want_input_grad"),
-        py::arg("want_res_grad"));
+        py::arg("want_res_grad"), py::arg("negative_slope") = 0.0);
 
   m.def("bn_fused_local_eligible", &msbn::bn_fused_local_eligible,
         py::arg("input"), py::arg("weight"), py::arg("bias"),
@@ -77,12 +77,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("batch_norm_fwd_fused_local", &msbn::batch_norm_fwd_fused_local,
         py::arg("input"), py::arg("residual"), py::arg("weight"),
         py::arg("bias"), py::arg("eps"), py::arg("momentum"),
-        py::arg("running_mean"), py::arg("running_var"), py::arg("relu"));
+        py::arg("running_mean"), py::arg("running_var"), py::arg("relu"),
+        py::arg("negative_slope") = 0.0);
   m.def("batch_norm_bwd_fused_local", &msbn::batch_norm_bwd_fused_local,
         py::arg("grad_out"), py::arg("input"), py::arg("residual"),
         py::arg("mean"), py::arg("invstd"), py::arg("weight"),
         py::arg("coefs"), py::arg("relu_mask"), py::arg("want_res_grad"),
-        py::arg("weight_g"), py::arg("bias_g"));
+        py::arg("weight_g"), py::arg("bias_g"),
+        py::arg("negative_slope") = 0.0);
 
   // ---- DDP machinery ----
   m.def("compute_bucket_assignment_by_size",
