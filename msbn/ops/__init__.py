@@ -292,8 +292,35 @@ def batch_norm_frozen_backward_elemt(grad_out, input, residual, coefs,
     )
 
 
+def launch_plan(kind: str, input: torch.Tensor, others=(), coefs=None) -> dict:
+    """What a GPU op WOULD launch for these tensors — host-only, launches
+    nothing.  The numbers come from the same host code the ops launch with.
+
+    ``kind`` / tensors (pass only what the op itself would dereference):
+      ``"stats"``             input = x
+      ``"bwd_reduce"``        input = x, others = (grad_out, residual, gm_out)
+      ``"elemt"``             input = x, others = (residual,), coefs
+      ``"bwd_elemt"``         input = x, others = (grad_out, residual), coefs
+      ``"frozen_bwd_elemt"``  input = grad_out, others = (x, residual), coefs
+      ``"fused_local"``       input = x, others = (residual,)
+    ``None`` entries of ``others`` are absent tensors.
+
+    Returns a dict with ``path`` (``"nchw_vec"``, ``"nchw_flat"``, ``"nhwc"``,
+    ``"small_plane"``, or ``"ineligible"`` for ``fused_local``), ``V`` and
+    ``trips`` (the most loop iterations any one thread makes); reductions add
+    ``nchunks``, ``flush_every``, ``finalize_trips`` and their chunk sizes,
+    elementwise ops add ``grid``, ``packs`` and ``multi_trip``."""
+    path, numbers = _require_hip().launch_plan(kind, input, list(others), coefs)
+    plan = dict(numbers)
+    plan["path"] = path
+    if "multi_trip" in plan:
+        plan["multi_trip"] = bool(plan["multi_trip"])
+    return plan
+
+
 __all__ = [
     "hip_available",
+    "launch_plan",
     "bn_frozen_coefs",
     "batch_norm_frozen_backward_elemt",
     "batch_norm_elemt_act",

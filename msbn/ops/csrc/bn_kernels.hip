@@ -6,8 +6,11 @@
 //  * Reductions are TWO-STAGE: a `partial` kernel with a grid sized for the
 //    256-CU chip (the stock one-block-per-channel shape leaves 3/4 of the chip
 //    idle at C=64) writes per-chunk fp64 {sum, sumsq} pairs to a workspace; a
-//    tiny `finalize` kernel combines them.  Deterministic (no atomics), and
-//    fp64 accumulation kills the E[x^2]-E[x]^2 cancellation risk outright.
+//    tiny `finalize` kernel combines them.  Deterministic (no atomics).  The
+//    stats partials sum short fp32 chunks into fp64; a chunk whose raw sums
+//    are ill-conditioned (mean^2/var > 64) is summed again around its own
+//    mean and un-shifted in fp64 (common.hpp), so the error of
+//    E[x^2]-E[x]^2 stays near the fp64 conditioning of the data.
 //  * wave64 shuffle reductions + LDS partials inside each block.
 //  * 16 B/lane vectorized loads (Pack<T,V>) for bf16/fp16/fp32, NCHW and
 //    channels-last (NHWC) layouts both first-class.
@@ -24,6 +27,9 @@
 #include <c10/hip/HIPStream.h>
 
 #include <algorithm>
+#include <map>
+#include <string>
+#include <vector>
 
 namespace msbn {
 
@@ -31,7 +37,12 @@ namespace {
 
 // =====================================================================
 // stats partial: NCHW   grid(C, nchunkN, nchunkS) block 256
-// ws layout: [nchunk][C][2] fp64, chunk = by*gridDim.z + bz
+// ws layout: [C][nchunk][2] fp64, chunk = by*gridDim.z + bz
+//
+// Each block first sums raw {x, x^2} (AccPair, common.hpp).  If its chunk
+// turns out ill-conditioned (needs_recentre) it reads the chunk a second
+// time and sums d = x - pivot with pivot = the chunk's own mean, then
+// un-shifts in fp64; the workspace holds plain {sum x, sum x^2} either way.
 // =====================================================================
 template <typename T, int V>
 __global__ void bn_stats_partial_nchw(const T* __restrict__ x,
@@ -43,35 +54,55 @@ __global__ void bn_stats_partial_nchw(const T* __restrict__ x,
   const int64_t n1 = i64min(n0 + chunkN, N);
   const int64_t s0 = blockIdx.z * chunkS;
   const int64_t s1 = i64min(s0 + chunkS, S);
-  AccPair acc;
-  int since_flush = 0;
-  for (int64_t n = n0; n < n1; ++n) {
-    const T* row = x + (n * C + c) * S;
-    if (V == 1) {
-      for (int64_t s = s0 + threadIdx.x; s < s1; s += blockDim.x) {
-        acc.add(to_f(nt_load1(&row[s])));
-        if (++since_flush == MSBN_ACC_FLUSH) {
-          acc.flush();
-          since_flush = 0;
+  __shared__ double lds[2 * (MSBN_BLOCK / MSBN_WAVE)];
+  __shared__ float pivot_s[2];  // {recentre?, pivot}
+  float pivot = 0.f;
+  double a = 0.0, b = 0.0;
+  for (int pass = 0; pass < 2; ++pass) {
+    AccPair acc;
+    int since_flush = 0;
+    for (int64_t n = n0; n < n1; ++n) {
+      const T* row = x + (n * C + c) * S;
+      if (V == 1) {
+        for (int64_t s = s0 + threadIdx.x; s < s1; s += blockDim.x) {
+          acc.add(to_f(nt_load1(&row[s])) - pivot);
+          if (++since_flush == MSBN_ACC_FLUSH) {
+            acc.flush();
+            since_flush = 0;
+          }
         }
-      }
-    } else {
-      for (int64_t s = s0 + (int64_t)threadIdx.x * V; s < s1;
-           s += (int64_t)blockDim.x * V) {
-        Pack<T, V> pk = nt_load<T, V>(&row[s]);
+      } else {
+        for (int64_t s = s0 + (int64_t)threadIdx.x * V; s < s1;
+             s += (int64_t)blockDim.x * V) {
+          Pack<T, V> pk = nt_load<T, V>(&row[s]);
 #pragma unroll
-        for (int k = 0; k < V; ++k) acc.add(to_f(pk.v[k]));
-        if (++since_flush == MSBN_ACC_FLUSH / V) {
-          acc.flush();
-          since_flush = 0;
+          for (int k = 0; k < V; ++k) acc.add(to_f(pk.v[k]) - pivot);
+          if (++since_flush == MSBN_ACC_FLUSH / V) {
+            acc.flush();
+            since_flush = 0;
+          }
         }
       }
     }
+    acc.flush();
+    a = acc.a;
+    b = acc.b;
+    if (pass) __syncthreads();  // lds is reused
+    block_reduce_pair(a, b, lds);
+    const double cnt = (double)((n1 - n0) * (s1 - s0));
+    if (pass) {
+      if (threadIdx.x == 0) unshift_pair(a, b, pivot, cnt);
+      break;
+    }
+    if (threadIdx.x == 0) {
+      const bool re = needs_recentre(a, b, cnt);
+      pivot_s[0] = re ? 1.f : 0.f;
+      pivot_s[1] = re ? (float)(a / cnt) : 0.f;
+    }
+    __syncthreads();
+    if (pivot_s[0] == 0.f) break;
+    pivot = pivot_s[1];
   }
-  acc.flush();
-  double a = acc.a, b = acc.b;
-  __shared__ double lds[2 * (MSBN_BLOCK / MSBN_WAVE)];
-  block_reduce_pair(a, b, lds);
   if (threadIdx.x == 0) {
     const int64_t chunk = (int64_t)blockIdx.y * gridDim.z + blockIdx.z;
     double* out = ws + (c * gridDim.y * gridDim.z + chunk) * 2;
@@ -92,20 +123,40 @@ __global__ void bn_stats_partial_nchw_flat(const T* __restrict__ x,
   const int64_t NS = N * S;
   const int64_t p0 = (int64_t)blockIdx.y * chunk_len;
   const int64_t p1 = i64min(p0 + chunk_len, NS);
-  AccPair acc;
-  int since_flush = 0;
-  for (int64_t p = p0 + threadIdx.x; p < p1; p += blockDim.x) {
-    const int64_t n = p / S, s = p - n * S;
-    acc.add(to_f(nt_load1(&x[(n * C + c) * S + s])));
-    if (++since_flush == MSBN_ACC_FLUSH) {
-      acc.flush();
-      since_flush = 0;
-    }
-  }
-  acc.flush();
-  double a = acc.a, b = acc.b;
   __shared__ double lds[2 * (MSBN_BLOCK / MSBN_WAVE)];
-  block_reduce_pair(a, b, lds);
+  __shared__ float pivot_s[2];  // {recentre?, pivot}
+  float pivot = 0.f;
+  double a = 0.0, b = 0.0;
+  for (int pass = 0; pass < 2; ++pass) {
+    AccPair acc;
+    int since_flush = 0;
+    for (int64_t p = p0 + threadIdx.x; p < p1; p += blockDim.x) {
+      const int64_t n = p / S, s = p - n * S;
+      acc.add(to_f(nt_load1(&x[(n * C + c) * S + s])) - pivot);
+      if (++since_flush == MSBN_ACC_FLUSH) {
+        acc.flush();
+        since_flush = 0;
+      }
+    }
+    acc.flush();
+    a = acc.a;
+    b = acc.b;
+    if (pass) __syncthreads();  // lds is reused
+    block_reduce_pair(a, b, lds);
+    const double cnt = (double)(p1 - p0);
+    if (pass) {
+      if (threadIdx.x == 0) unshift_pair(a, b, pivot, cnt);
+      break;
+    }
+    if (threadIdx.x == 0) {
+      const bool re = needs_recentre(a, b, cnt);
+      pivot_s[0] = re ? 1.f : 0.f;
+      pivot_s[1] = re ? (float)(a / cnt) : 0.f;
+    }
+    __syncthreads();
+    if (pivot_s[0] == 0.f) break;
+    pivot = pivot_s[1];
+  }
   if (threadIdx.x == 0) {
     double* out = ws + (c * gridDim.y + blockIdx.y) * 2;
     out[0] = a;
@@ -117,6 +168,8 @@ __global__ void bn_stats_partial_nchw_flat(const T* __restrict__ x,
 // stats partial: NHWC   grid(ctiles, nchunk) block 256
 // Each block covers channels [tile*lpr*V, ...) and a chunk of rows; thread
 // (lane, rowoff) owns V consecutive channels.  LDS tree-reduce over rowoff.
+// Same two passes as the NCHW kernel, decided per (block, channel); the
+// second pass runs only if some channel of the block needs it.
 // =====================================================================
 template <typename T, int V>
 __global__ void bn_stats_partial_nhwc(const T* __restrict__ x,
@@ -128,63 +181,108 @@ __global__ void bn_stats_partial_nhwc(const T* __restrict__ x,
   const bool active = rowoff < rpi;
   const int64_t c = (int64_t)blockIdx.x * lpr * V + (int64_t)lane * V;
   const bool inb = active && (c + V <= C);
+  const int64_t r0 = (int64_t)blockIdx.y * chunk_rows;
+  const int64_t r1 = i64min(r0 + chunk_rows, rows);
 
-  AccPair acc[V];
-
-  if (inb) {
-    const int64_t r0 = (int64_t)blockIdx.y * chunk_rows;
-    const int64_t r1 = i64min(r0 + chunk_rows, rows);
-    int since_flush = 0;
-    for (int64_t r = r0 + rowoff; r < r1; r += rpi) {
-      Pack<T, V> pk = nt_load<T, V>(&x[r * C + c]);
-#pragma unroll
-      for (int k = 0; k < V; ++k) acc[k].add(to_f(pk.v[k]));
-      if (++since_flush == MSBN_ACC_FLUSH) {
-#pragma unroll
-        for (int k = 0; k < V; ++k) acc[k].flush();
-        since_flush = 0;
-      }
-    }
-  }
-  double a[V], b[V];
-#pragma unroll
-  for (int k = 0; k < V; ++k) {
-    acc[k].flush();
-    a[k] = acc[k].a;
-    b[k] = acc[k].b;
-  }
-
-  // LDS tree-reduce across the rowoff dimension (generic, non-pow2 safe).
   // LDS layout [k][tid] with separate sum/sumsq planes: lane l of a wave
   // lands on bank (2*l) mod 64 for ds_*_b64 -> conflict-free (the [tid][k]
   // layout measured ~20 extra LDS cycles/instr via SQ_LDS_BANK_CONFLICT).
   __shared__ double sdata[MSBN_BLOCK * V * 2];
+
+  float pivot[V];
+  bool re[V];
 #pragma unroll
   for (int k = 0; k < V; ++k) {
-    sdata[k * MSBN_BLOCK + threadIdx.x] = a[k];
-    sdata[(V + k) * MSBN_BLOCK + threadIdx.x] = b[k];
+    pivot[k] = 0.f;
+    re[k] = false;
   }
-  for (int st = 1; st < rpi; st <<= 1) {
-    __syncthreads();
-    if (active && (rowoff & ((st << 1) - 1)) == 0 && rowoff + st < rpi) {
-      const int other = threadIdx.x + st * lpr;
+
+  for (int pass = 0; pass < 2; ++pass) {
+    AccPair acc[V];
+    if (inb) {
+      int since_flush = 0;
+      for (int64_t r = r0 + rowoff; r < r1; r += rpi) {
+        Pack<T, V> pk = nt_load<T, V>(&x[r * C + c]);
 #pragma unroll
-      for (int k = 0; k < V; ++k) {
-        sdata[k * MSBN_BLOCK + threadIdx.x] += sdata[k * MSBN_BLOCK + other];
-        sdata[(V + k) * MSBN_BLOCK + threadIdx.x] +=
-            sdata[(V + k) * MSBN_BLOCK + other];
+        for (int k = 0; k < V; ++k) acc[k].add(to_f(pk.v[k]) - pivot[k]);
+        if (++since_flush == MSBN_ACC_FLUSH) {
+#pragma unroll
+          for (int k = 0; k < V; ++k) acc[k].flush();
+          since_flush = 0;
+        }
       }
     }
-  }
-  __syncthreads();
-  if (rowoff == 0 && c < C) {
-    const int64_t chunk = blockIdx.y;
+    double a[V], b[V];
 #pragma unroll
     for (int k = 0; k < V; ++k) {
-      if (c + k < C) {
-        double* out = ws + ((c + k) * gridDim.y + chunk) * 2;
-        out[0] = sdata[k * MSBN_BLOCK + threadIdx.x];
-        out[1] = sdata[(V + k) * MSBN_BLOCK + threadIdx.x];
+      acc[k].flush();
+      a[k] = acc[k].a;
+      b[k] = acc[k].b;
+    }
+    // second pass: undo the shift per thread, over the rows it summed
+    if (pass && inb && r0 + rowoff < r1) {
+      const double cnt = (double)((r1 - r0 - rowoff + rpi - 1) / rpi);
+#pragma unroll
+      for (int k = 0; k < V; ++k) unshift_pair(a[k], b[k], pivot[k], cnt);
+    }
+
+    // LDS tree-reduce across the rowoff dimension (generic, non-pow2 safe).
+    if (pass) __syncthreads();  // sdata is reused
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+      sdata[k * MSBN_BLOCK + threadIdx.x] = a[k];
+      sdata[(V + k) * MSBN_BLOCK + threadIdx.x] = b[k];
+    }
+    for (int st = 1; st < rpi; st <<= 1) {
+      __syncthreads();
+      if (active && (rowoff & ((st << 1) - 1)) == 0 && rowoff + st < rpi) {
+        const int other = threadIdx.x + st * lpr;
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+          sdata[k * MSBN_BLOCK + threadIdx.x] += sdata[k * MSBN_BLOCK + other];
+          sdata[(V + k) * MSBN_BLOCK + threadIdx.x] +=
+              sdata[(V + k) * MSBN_BLOCK + other];
+        }
+      }
+    }
+    __syncthreads();
+    int any = 0;
+    if (rowoff == 0 && c < C) {
+      const int64_t chunk = blockIdx.y;
+      const double cnt = (double)(r1 - r0);
+#pragma unroll
+      for (int k = 0; k < V; ++k) {
+        if (c + k < C) {
+          const double sa = sdata[k * MSBN_BLOCK + threadIdx.x];
+          const double sb = sdata[(V + k) * MSBN_BLOCK + threadIdx.x];
+          bool want = false;
+          if (!pass) {
+            want = needs_recentre(sa, sb, cnt);
+            // publish {recentre?, pivot} in this thread's own sdata slots
+            // (threadIdx.x == lane here); read back after the barrier below
+            sdata[k * MSBN_BLOCK + threadIdx.x] = want ? 1.0 : 0.0;
+            sdata[(V + k) * MSBN_BLOCK + threadIdx.x] = want ? sa / cnt : 0.0;
+            any |= want ? 1 : 0;
+          }
+          // first pass: every channel that is fine as it is; second pass:
+          // the re-centred ones
+          if (pass ? re[k] : !want) {
+            double* out = ws + ((c + k) * gridDim.y + chunk) * 2;
+            out[0] = sa;
+            out[1] = sb;
+          }
+        }
+      }
+    }
+    if (pass) break;
+    if (!__syncthreads_or(any)) break;  // block-uniform; publishes sdata
+    if (inb) {
+#pragma unroll
+      for (int k = 0; k < V; ++k) {
+        re[k] = sdata[k * MSBN_BLOCK + lane] != 0.0;
+        // channels that were fine keep pivot 0: their second-pass sums are
+        // simply not stored
+        pivot[k] = re[k] ? (float)sdata[(V + k) * MSBN_BLOCK + lane] : 0.f;
       }
     }
   }
@@ -1139,15 +1237,16 @@ FlatGrid flat_grid(int64_t C, int64_t NS, int64_t target_blocks) {
 }
 
 // pick vector width: 16B/lane when layout & alignment allow
-template <typename T>
-int pick_v(const void* p0, const void* p1, const void* p2, int64_t inner) {
-  const int vmax = 16 / (int)sizeof(T);
+// `ptrs` is EVERY tensor pointer the launch dereferences with V-wide packs
+// (absent ones nullptr); esize the element size in bytes.
+int pick_v(int esize, c10::ArrayRef<const void*> ptrs, int64_t inner) {
+  const int vmax = 16 / esize;
   auto ok = [&](int v) {
-    const size_t bytes = (size_t)v * sizeof(T);
-    auto aligned = [&](const void* p) {
-      return p == nullptr || ((uintptr_t)p % bytes) == 0;
-    };
-    return inner % v == 0 && aligned(p0) && aligned(p1) && aligned(p2);
+    const size_t bytes = (size_t)v * esize;
+    if (inner % v != 0) return false;
+    for (const void* p : ptrs)
+      if (p != nullptr && ((uintptr_t)p % bytes) != 0) return false;
+    return true;
   };
   if (ok(vmax)) return vmax;
   if (vmax >= 4 && ok(vmax / 2)) return vmax / 2;
@@ -1225,6 +1324,73 @@ NhwcGrid nhwc_grid(int64_t rows, int64_t C, int V) {
 int elemt_grid(int64_t total, int V) {
   return (int)std::min<int64_t>(cdiv(total, (int64_t)MSBN_BLOCK * V),
                                 2 * kTargetBlocks);
+}
+
+// ---- launch plans -----------------------------------------------------
+// The one place a launch's vector width and grid are decided: the ops below
+// launch from these, and launch_plan() reports them to tests (so a test can
+// prove which loop trips / branches its shape reaches).
+enum class RedPath { NchwVec, NchwFlat, Nhwc };
+
+struct ReducePlan {
+  RedPath path;
+  int v;
+  int nchunks;        // partials per channel handed to the finalize kernel
+  NchwGrid nchw;      // path == NchwVec
+  FlatGrid flat;      // path == NchwFlat
+  NhwcGrid nhwc;      // path == Nhwc
+  int64_t trips;      // most iterations any thread's accumulation loop makes
+  int flush_every;    // iterations between two AccPair flushes
+};
+
+ReducePlan plan_reduce(const Layout& L, int esize,
+                       c10::ArrayRef<const void*> ptrs) {
+  ReducePlan p{};
+  if (!L.nhwc) {
+    p.v = pick_v(esize, ptrs, L.S);
+    if (p.v == 1) {
+      p.path = RedPath::NchwFlat;
+      p.flat = flat_grid(L.C, L.rows, kTargetBlocks);
+      p.nchunks = p.flat.nchunks;
+      p.trips = cdiv(p.flat.chunk_len, MSBN_BLOCK);
+      p.flush_every = MSBN_ACC_FLUSH;
+    } else {
+      p.path = RedPath::NchwVec;
+      p.nchw = nchw_grid(L.N, L.C, L.S, p.v);
+      p.nchunks = p.nchw.nchunks;
+      p.trips = p.nchw.chunkN *
+                cdiv(std::min(p.nchw.chunkS, L.S), (int64_t)MSBN_BLOCK * p.v);
+      p.flush_every = MSBN_ACC_FLUSH / p.v;
+    }
+  } else {
+    p.path = RedPath::Nhwc;
+    p.v = pick_v(esize, ptrs, L.C);
+    p.nhwc = nhwc_grid(L.rows, L.C, p.v);
+    p.nchunks = p.nhwc.nchunks;
+    p.trips = cdiv(p.nhwc.chunk_rows, MSBN_BLOCK / p.nhwc.lpr);
+    p.flush_every = MSBN_ACC_FLUSH;
+  }
+  return p;
+}
+
+struct ElemtPlan {
+  int v;
+  int grid;
+  int64_t packs;  // V-wide packs in the tensor; one thread-trip handles one
+};
+
+// `coef` is the caller-visible per-channel fp32 buffer ([scale | shift]) the
+// NHWC kernels load V floats at a time; nullptr when none is read.
+ElemtPlan plan_elemt(const Layout& L, int64_t total, int esize,
+                     c10::ArrayRef<const void*> ptrs, const float* coef) {
+  ElemtPlan p{};
+  p.v = pick_v(esize, ptrs, L.nhwc ? L.C : L.S);
+  if (L.nhwc && coef != nullptr &&
+      ((uintptr_t)coef % ((size_t)p.v * sizeof(float))) != 0)
+    p.v = 1;
+  p.grid = elemt_grid(total, p.v);
+  p.packs = cdiv(total, p.v);
+  return p;
 }
 
 #define MSBN_DISPATCH_FLOAT_TYPES(TYPE, NAME, ...)                          \
@@ -1349,36 +1515,26 @@ void stats_into(const at::Tensor& input, double eps, float* mean_p,
     const native_t* x =
         reinterpret_cast<const native_t*>(input.data_ptr<scalar_t>());
     constexpr int VMAX = 16 / (int)sizeof(native_t);
-    at::Tensor ws;
-    int nchunks = 0;
-    if (!L.nhwc) {
-      const int v = pick_v<native_t>(x, nullptr, nullptr, L.S);
-      if (v == 1) {
-        auto g = flat_grid(L.C, L.rows, kTargetBlocks);
-        nchunks = g.nchunks;
-        ws = at::empty({(int64_t)nchunks * L.C * 2},
-                       input.options().dtype(at::kDouble));
-        hipLaunchKernelGGL((bn_stats_partial_nchw_flat<native_t>), g.grid,
-                           dim3(MSBN_BLOCK), 0, stream, x,
-                           ws.data_ptr<double>(), L.N, L.C, L.S, g.chunk_len);
-      } else {
-      auto g = nchw_grid(L.N, L.C, L.S, v);
-      nchunks = g.nchunks;
-      ws = at::empty({(int64_t)nchunks * L.C * 2},
-                     input.options().dtype(at::kDouble));
+    const ReducePlan plan = plan_reduce(L, (int)sizeof(native_t), {x});
+    const int v = plan.v;
+    const int nchunks = plan.nchunks;
+    at::Tensor ws = at::empty({(int64_t)nchunks * L.C * 2},
+                              input.options().dtype(at::kDouble));
+    if (plan.path == RedPath::NchwFlat) {
+      const auto& g = plan.flat;
+      hipLaunchKernelGGL((bn_stats_partial_nchw_flat<native_t>), g.grid,
+                         dim3(MSBN_BLOCK), 0, stream, x,
+                         ws.data_ptr<double>(), L.N, L.C, L.S, g.chunk_len);
+    } else if (plan.path == RedPath::NchwVec) {
+      const auto& g = plan.nchw;
       MSBN_DISPATCH_V(v, VMAX, [&] {
         hipLaunchKernelGGL((bn_stats_partial_nchw<native_t, VV>), g.grid,
                            dim3(MSBN_BLOCK), 0, stream, x,
                            ws.data_ptr<double>(), L.N, L.C, L.S, g.chunkN,
                            g.chunkS);
       });
-      }
     } else {
-      const int v = pick_v<native_t>(x, nullptr, nullptr, L.C);
-      auto g = nhwc_grid(L.rows, L.C, v);
-      nchunks = g.nchunks;
-      ws = at::empty({(int64_t)nchunks * L.C * 2},
-                     input.options().dtype(at::kDouble));
+      const auto& g = plan.nhwc;
       MSBN_DISPATCH_V(v, VMAX, [&] {
         hipLaunchKernelGGL((bn_stats_partial_nhwc<native_t, VV>), g.grid,
                            dim3(MSBN_BLOCK), 0, stream, x,
@@ -1674,9 +1830,10 @@ at::Tensor batch_norm_elemt_act(const at::Tensor& input,
                 : nullptr;
     native_t* y = reinterpret_cast<native_t*>(out.data_ptr<scalar_t>());
     constexpr int VMAX = 16 / (int)sizeof(native_t);
-    const int64_t inner = L.nhwc ? L.C : L.S;
-    const int v = pick_v<native_t>(x, y, res, inner);
-    const int grid = elemt_grid(total, v);
+    const ElemtPlan plan =
+        plan_elemt(L, total, (int)sizeof(native_t), {x, y, res}, scale);
+    const int v = plan.v;
+    const int grid = plan.grid;
     MSBN_DISPATCH_V(v, VMAX, [&] {
       MSBN_DISPATCH_ACT(act, ACT_, [&] {
         MSBN_DISPATCH_BOOL(has_res, RES_, [&] {
@@ -1778,28 +1935,26 @@ batch_norm_backward_reduce_act(
     native_t* gm =
         want_gm ? reinterpret_cast<native_t*>(gm_out->data_ptr()) : nullptr;
     constexpr int VMAX = 16 / (int)sizeof(native_t);
-    at::Tensor ws;
-    int nchunks = 0;
+    // every pointer the partial kernel dereferences, gm_out included
+    const ReducePlan plan =
+        plan_reduce(L, (int)sizeof(native_t), {x, dy, res, gm});
+    const int v = plan.v;
+    const int nchunks = plan.nchunks;
+    at::Tensor ws = at::empty({(int64_t)nchunks * L.C * 2},
+                              input.options().dtype(at::kDouble));
     MSBN_DISPATCH_ACT(act, ACT_, [&] {
       MSBN_DISPATCH_BOOL(has_res, RES_, [&] {
         MSBN_DISPATCH_BOOL(want_gm, GM_, [&] {
         if (!L.nhwc) {
-          const int v = pick_v<native_t>(x, dy, res, L.S);
-          if (v == 1) {
-            auto g = flat_grid(L.C, L.rows, kTargetBlocks);
-            nchunks = g.nchunks;
-            ws = at::empty({(int64_t)nchunks * L.C * 2},
-                           input.options().dtype(at::kDouble));
+          if (plan.path == RedPath::NchwFlat) {
+            const auto& g = plan.flat;
             hipLaunchKernelGGL(
                 (bn_bwd_reduce_partial_nchw_flat<native_t, ACT_, RES_, GM_>),
                 g.grid, dim3(MSBN_BLOCK), 0, stream, dy, x, res, gm,
                 mean.data_ptr<float>(), scale, shift, ws.data_ptr<double>(),
                 L.N, L.C, L.S, g.chunk_len, slope);
           } else {
-            auto g = nchw_grid(L.N, L.C, L.S, v);
-            nchunks = g.nchunks;
-            ws = at::empty({(int64_t)nchunks * L.C * 2},
-                           input.options().dtype(at::kDouble));
+            const auto& g = plan.nchw;
             MSBN_DISPATCH_V(v, VMAX, [&] {
               hipLaunchKernelGGL(
                   (bn_bwd_reduce_partial_nchw<native_t, VV, ACT_, RES_, GM_>),
@@ -1809,11 +1964,7 @@ batch_norm_backward_reduce_act(
             });
           }
         } else {
-          const int v = pick_v<native_t>(x, dy, res, L.C);
-          auto g = nhwc_grid(L.rows, L.C, v);
-          nchunks = g.nchunks;
-          ws = at::empty({(int64_t)nchunks * L.C * 2},
-                         input.options().dtype(at::kDouble));
+          const auto& g = plan.nhwc;
           MSBN_DISPATCH_V(v, VMAX, [&] {
             hipLaunchKernelGGL(
                 (bn_bwd_reduce_partial_nhwc<native_t, VV, ACT_, RES_, GM_>),
@@ -1921,9 +2072,11 @@ std::tuple<at::Tensor, at::Tensor> batch_norm_backward_elemt_act(
                        ? reinterpret_cast<native_t*>(dres.data_ptr<scalar_t>())
                        : nullptr;
     constexpr int VMAX = 16 / (int)sizeof(native_t);
-    const int64_t inner = L.nhwc ? L.C : L.S;
-    const int v = pick_v<native_t>(x, dy, o, inner);
-    const int grid = elemt_grid(total, v);
+    // every pointer the launch touches (absent ones are nullptr)
+    const ElemtPlan plan = plan_elemt(L, total, (int)sizeof(native_t),
+                                      {x, dy, res, o, dr}, scale);
+    const int v = plan.v;
+    const int grid = plan.grid;
     MSBN_DISPATCH_V(v, VMAX, [&] {
       MSBN_DISPATCH_ACT(act, ACT_, [&] {
         MSBN_DISPATCH_BOOL(has_res, RES_, [&] {
@@ -2067,13 +2220,12 @@ std::tuple<at::Tensor, at::Tensor> batch_norm_frozen_backward_elemt(
         resg ? reinterpret_cast<native_t*>(dres.data_ptr<scalar_t>())
              : nullptr;
     constexpr int VMAX = 16 / (int)sizeof(native_t);
-    const int64_t inner = L.nhwc ? L.C : L.S;
-    // every pointer the launch touches (absent ones are nullptr)
-    int v = std::min(pick_v<native_t>(dy, x, res, inner),
-                     pick_v<native_t>(o, dr, nullptr, inner));
-    // NHWC packs load V fp32 coefficients at once
-    if (L.nhwc && ((uintptr_t)scale % ((size_t)v * sizeof(float))) != 0) v = 1;
-    const int grid = elemt_grid(total, v);
+    // every pointer the launch touches (absent ones are nullptr); NHWC
+    // packs load V fp32 coefficients at once, hence `scale`
+    const ElemtPlan plan = plan_elemt(L, total, (int)sizeof(native_t),
+                                      {dy, x, res, o, dr}, scale);
+    const int v = plan.v;
+    const int grid = plan.grid;
     MSBN_DISPATCH_V(v, VMAX, [&] {
       auto launch = [&](auto act_c, auto res_c, auto resg_c) {
         constexpr int ACT_ = decltype(act_c)::value;
@@ -2195,7 +2347,7 @@ batch_norm_fwd_fused_local(const at::Tensor& input,
                 : nullptr;
     native_t* yp = reinterpret_cast<native_t*>(y.data_ptr<scalar_t>());
     constexpr int VMAX = 16 / (int)sizeof(native_t);
-    const int v = pick_v<native_t>(x, res, yp, S);
+    const int v = pick_v((int)sizeof(native_t), {x, res, yp}, S);
     MSBN_DISPATCH_V(v, VMAX, [&] {
       MSBN_DISPATCH_ACT(act_mode(relu, slope), ACT_, [&] {
         MSBN_DISPATCH_BOOL(has_res, RES_, [&] {
@@ -2258,9 +2410,8 @@ batch_norm_bwd_fused_local(const at::Tensor& grad_out, const at::Tensor& input,
                         ? reinterpret_cast<native_t*>(dres.data_ptr<scalar_t>())
                         : nullptr;
     constexpr int VMAX = 16 / (int)sizeof(native_t);
-    const int v0 = pick_v<native_t>(dy, x, res, S);
-    const int v1 = pick_v<native_t>(dxp, drp, nullptr, S);
-    const int v = std::min(v0, v1);
+    const int v =
+        pick_v((int)sizeof(native_t), {dy, x, res, dxp, drp}, S);
     MSBN_DISPATCH_V(v, VMAX, [&] {
       auto launch = [&](auto act_c, auto res_c, auto resg_c) {
         hipLaunchKernelGGL(
@@ -2292,6 +2443,81 @@ batch_norm_bwd_fused_local(const at::Tensor& grad_out, const at::Tensor& input,
     });
   });
   return {dx, gw, gb, dres};
+}
+
+// ---------------------------------------------------------------------------
+// launch_plan: host-only; launches nothing.  Reports, from the SAME helpers
+// the ops launch with (get_layout, plan_reduce / plan_elemt -> pick_v, *_grid,
+// bn_fused_local_eligible), which kernel path a call would take and how far
+// its loops run.  Output tensors the ops allocate themselves are taken as
+// allocator-aligned.
+// ---------------------------------------------------------------------------
+std::tuple<std::string, std::map<std::string, int64_t>> launch_plan(
+    const std::string& kind, const at::Tensor& input,
+    const std::vector<c10::optional<at::Tensor>>& others,
+    const c10::optional<at::Tensor>& coefs) {
+  TORCH_CHECK(input.dim() >= 2 && input.numel() > 0,
+              "launch_plan: input must be a non-empty >= 2-D tensor");
+  const int esize = (int)input.element_size();
+  TORCH_CHECK(esize == 2 || esize == 4, "launch_plan: unsupported dtype");
+  std::vector<const void*> ptrs{input.data_ptr()};
+  for (const auto& t : others)
+    if (t.has_value() && t->defined()) ptrs.push_back(t->data_ptr());
+  const float* coef = coefs.has_value() && coefs->defined()
+                          ? coefs->data_ptr<float>()
+                          : nullptr;
+  std::map<std::string, int64_t> d;
+  std::string path;
+
+  if (kind == "fused_local") {
+    if (!bn_fused_local_eligible(input, c10::nullopt, c10::nullopt,
+                                 c10::nullopt, c10::nullopt))
+      return {"ineligible", d};
+    const int64_t C = input.size(1);
+    const int64_t plane = input.numel() / C;
+    const int64_t S = plane / input.size(0);
+    d["V"] = pick_v(esize, ptrs, S);
+    d["trips"] = cdiv(plane / d["V"], MSBN_BLOCK);
+    d["blocks"] = C;
+    return {"small_plane", d};
+  }
+
+  const Layout L = get_layout(input);
+  if (kind == "stats" || kind == "bwd_reduce") {
+    const ReducePlan p = plan_reduce(L, esize, ptrs);
+    path = p.path == RedPath::Nhwc       ? "nhwc"
+           : p.path == RedPath::NchwFlat ? "nchw_flat"
+                                         : "nchw_vec";
+    d["V"] = p.v;
+    d["nchunks"] = p.nchunks;
+    d["trips"] = p.trips;
+    d["flush_every"] = p.flush_every;
+    d["finalize_trips"] = cdiv(p.nchunks, MSBN_WAVE);
+    if (p.path == RedPath::NchwVec) {
+      d["chunkN"] = p.nchw.chunkN;
+      d["chunkS"] = p.nchw.chunkS;
+      d["nchunkS"] = p.nchw.grid.z;
+    } else if (p.path == RedPath::NchwFlat) {
+      d["chunk_len"] = p.flat.chunk_len;
+    } else {
+      d["chunk_rows"] = p.nhwc.chunk_rows;
+      d["lpr"] = p.nhwc.lpr;
+      d["ctiles"] = p.nhwc.grid.x;
+    }
+    return {path, d};
+  }
+  TORCH_CHECK(kind == "elemt" || kind == "bwd_elemt" ||
+                  kind == "frozen_bwd_elemt",
+              "launch_plan: unknown kind '", kind, "'");
+  const ElemtPlan p = plan_elemt(L, input.numel(), esize, ptrs, coef);
+  path = L.nhwc ? "nhwc" : (p.v == 1 ? "nchw_flat" : "nchw_vec");
+  const int64_t threads = (int64_t)p.grid * MSBN_BLOCK;
+  d["V"] = p.v;
+  d["grid"] = p.grid;
+  d["packs"] = p.packs;
+  d["trips"] = cdiv(p.packs, threads);
+  d["multi_trip"] = p.packs > threads ? 1 : 0;
+  return {path, d};
 }
 
 }  // namespace msbn

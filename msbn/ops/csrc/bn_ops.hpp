@@ -6,7 +6,10 @@
 
 #include <ATen/ATen.h>
 
+#include <map>
+#include <string>
 #include <tuple>
+#include <vector>
 
 namespace msbn {
 
@@ -165,5 +168,24 @@ std::tuple<at::Tensor, at::Tensor> batch_norm_backward_elemt_act(
     const at::Tensor& sum_dy_xmu, const at::Tensor& count, bool relu_mask,
     bool want_res_grad, const c10::optional<at::Tensor>& coefs_in,
     double negative_slope);
+
+// ---- launch plan (host only, launches nothing) ----------------------------
+// Which kernel path a call would take and how far its loops run, decided by
+// the same host code the ops launch with.  kind / tensors:
+//   "stats"            input = x
+//   "bwd_reduce"       input = x,        others = {grad_out, residual, gm_out}
+//   "elemt"            input = x,        others = {residual},  coefs
+//   "bwd_elemt"        input = x,        others = {grad_out, residual}, coefs
+//   "frozen_bwd_elemt" input = grad_out, others = {x, residual}, coefs
+//   "fused_local"      input = x,        others = {residual}
+// (pass only what the op itself would dereference).  Returns (path, numbers):
+// path is "nchw_vec" | "nchw_flat" | "nhwc" | "small_plane" | "ineligible";
+// numbers always hold V and trips (most loop iterations of one thread);
+// reductions add nchunks, flush_every, finalize_trips and the chunk sizes,
+// elementwise ops add grid, packs and multi_trip.
+std::tuple<std::string, std::map<std::string, int64_t>> launch_plan(
+    const std::string& kind, const at::Tensor& input,
+    const std::vector<c10::optional<at::Tensor>>& others,
+    const c10::optional<at::Tensor>& coefs);
 
 }  // namespace msbn

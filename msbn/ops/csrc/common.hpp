@@ -3,9 +3,12 @@
 // Design notes (MI355X-first, per /opt/skills/guides/cdna_hip_programming.md):
 //  * wave64 is the scheduling quantum: all shuffle reductions are width-64.
 //  * memory-bound kernels vectorize loads to 16 B/lane (Pack<T,V>).
-//  * statistics accumulate in fp64 per-thread and across the two-stage
-//    (partial -> finalize) reduction: deterministic (no atomics) and immune
-//    to the sum-of-squares cancellation that plagues fp32 E[x^2] - E[x]^2.
+//  * statistics reduce deterministically (no atomics) through a two-stage
+//    (partial -> finalize) pipeline.  Each thread sums short fp32 chunks and
+//    flushes them into fp64 totals (AccPair below).  fp64 totals alone do not
+//    cure E[x^2]-E[x]^2 cancellation — raw squares are rounded in fp32 before
+//    they reach them — so an ill-conditioned chunk is summed a second time
+//    around its own mean (needs_recentre / unshift_pair below).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -183,9 +186,22 @@ __device__ __forceinline__ int64_t i64min(int64_t a, int64_t b) {
 // half-rate f64 ops per 16 B load caps the stats kernels at ~4.8 TB/s of
 // the 6.3 TB/s ceiling).  Accumulate a short fp32 chunk (<= kAccFlush loop
 // iterations) and FLUSH into the fp64 totals periodically: full-rate inner
-// loop, and the fp64 totals still kill E[x^2]-E[x]^2 cancellation.  fp32
-// chunk error is ~sqrt(n)*2^-24 over <=512 elements — far below the fp32
-// reference tolerance the tests compare against.
+// loop.
+//
+// What the fp64 totals do NOT do is protect {sum v, sum v*v} of raw values:
+// each v*v and each chunk add is rounded in fp32 (relative 2^-24 of v^2), so
+// var = E[x^2]-E[x]^2 loses mean^2/var of its digits before fp64 sees it
+// (mean 1000, std 1: invstd off by 1e-3..1e-2).  Hence:
+//   * the stats kernels sum raw values first — exact enough while
+//     mean^2/var <= MSBN_RAW_COND_MAX, which is what activations look like —
+//     and a block whose chunk fails that test (needs_recentre) reads the
+//     chunk again, sums d = x - pivot with pivot = the chunk's mean, and
+//     undoes the shift in fp64 (unshift_pair).  fp32 chunk error is then
+//     ~sqrt(n)*2^-24 relative to sum d^2 ~ n*var, i.e. of the variance;
+//   * the backward kernels add g and g*(x - mean) (add2), centred already.
+// Either way the workspace holds plain fp64 {sum x, sum x^2}; the finalize
+// kernels' E[x^2]-E[x]^2 then costs 2^-53 * mean^2/var, which is the
+// conditioning of the problem in fp64.
 #define MSBN_ACC_FLUSH 64
 
 struct AccPair {
@@ -206,5 +222,30 @@ struct AccPair {
     fa = fb = 0.f;
   }
 };
+
+// mean^2/var above which a chunk's raw {sum x, sum x^2} are not trusted and
+// the stats kernels re-read the chunk with shifted values.  The raw sums'
+// relative error in the variance is ~(1 + cond) * 2^-24; at 64 that is
+// still several times inside the 1e-5 the statistics are held to.  The raw
+// sums themselves decide: their variance is off by at most ~mean^2 * 1e-6,
+// so an ill-conditioned chunk cannot look well-conditioned.
+#define MSBN_RAW_COND_MAX 64.0
+
+__device__ __forceinline__ bool needs_recentre(double sum, double sumsq,
+                                               double cnt) {
+  // mean^2 <= K*var with mean = sum/cnt, var = sumsq/cnt - mean^2, cleared
+  // of its divisions: (K+1)*sum^2 <= K*cnt*sumsq.  False for var <= 0 (unless
+  // all is zero) and for NaN: re-centre.
+  return !((MSBN_RAW_COND_MAX + 1.0) * sum * sum <=
+           MSBN_RAW_COND_MAX * cnt * sumsq);
+}
+
+// {sum d, sum d^2} over cnt elements with d = x - pivot  ->  {sum x, sum x^2}
+__device__ __forceinline__ void unshift_pair(double& a, double& b,
+                                             float pivot, double cnt) {
+  const double p = (double)pivot;
+  b += p * (2.0 * a + cnt * p);
+  a += cnt * p;
+}
 
 }  // namespace msbn

@@ -86,6 +86,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("weight_g"), py::arg("bias_g"),
         py::arg("negative_slope") = 0.0);
 
+  m.def("launch_plan", &msbn::launch_plan, py::arg("kind"), py::arg("input"),
+        py::arg("others") = std::vector<c10::optional<at::Tensor>>(),
+        py::arg("coefs") = py::none());
+
   // ---- DDP machinery ----
   m.def("compute_bucket_assignment_by_size",
         &msbn::compute_bucket_assignment_by_size, py::arg("tensors"),

@@ -30,7 +30,9 @@ OP_SHAPES = [
     (2, 100, 5, 5),     # C not a multiple of 8
     (8, 16),            # 2-D input
     (2, 24, 4, 6, 5),   # 5-D / channels_last_3d
-    (2, 64, 56, 56),    # several blocks: the grid-stride loop
+    (2, 64, 56, 56),    # many blocks (1568 at V=1), still under the 4096-block
+                        # cap: ONE trip each.  The grid-stride loop's second
+                        # trip is covered in test_gpu_reduction_edges.py
 ]
 DTYPES = [torch.float32, torch.bfloat16, torch.float16]
 # (relu, with_res, want_res_grad)
