@@ -32,12 +32,36 @@ def _norm(planes, fused):
     return SyncBatchNorm(planes) if fused else BatchNorm2d(planes)
 
 
+def _split(x):
+    # a block's input: a tensor, or the (main, skip) pair of a forking block
+    return x if isinstance(x, tuple) else (x, x)
+
+
+def _last_bn(bn, x, identity, fork):
+    """A block's closing bn(+add)+relu.  ``fork``: the output feeds the next
+    block twice (its conv1 and its skip path), so return it as a (main, skip)
+    pair whose two gradients come back to this BN unsummed and are added
+    inside its backward reduce kernel (msbn/nn/fused.py) instead of by an
+    eager add over the whole tensor."""
+    if not fork:
+        return bn(x, residual=identity)
+    if isinstance(bn, SyncBatchNormAct2d):
+        return bn(x, residual=identity, fork=True)
+    # slot was swapped for another module (freeze_batchnorm): one gradient
+    y = bn(x, residual=identity)
+    return y, y
+
+
 class BasicBlock(nn.Module):
     expansion = 1
 
-    def __init__(self, cin, planes, stride=1, downsample=None, fused=False):
+    def __init__(self, cin, planes, stride=1, downsample=None, fused=False,
+                 fork=False):
         super().__init__()
         self.fused = fused
+        # fused only: return the output as a (main, skip) pair (see _last_bn);
+        # off by default, so a stand-alone block maps tensor -> tensor
+        self.fork = fork and fused
         self.conv1 = conv3x3(cin, planes, stride)
         self.conv2 = conv3x3(planes, planes)
         self.downsample = downsample
@@ -50,10 +74,13 @@ class BasicBlock(nn.Module):
             self.relu = nn.ReLU(inplace=True)
 
     def forward(self, x):
-        identity = self.downsample(x) if self.downsample is not None else x
+        x, skip = _split(x)
+        identity = (self.downsample(skip) if self.downsample is not None
+                    else skip)
         if self.fused:
             out = self.bn1(self.conv1(x))
-            return self.bn2(self.conv2(out), residual=identity)
+            return _last_bn(self.bn2, self.conv2(out), identity,
+                            getattr(self, "fork", False))
         out = self.relu(self.bn1(self.conv1(x)))
         out = self.bn2(self.conv2(out))
         return self.relu(out + identity)
@@ -62,9 +89,11 @@ class BasicBlock(nn.Module):
 class Bottleneck(nn.Module):
     expansion = 4
 
-    def __init__(self, cin, planes, stride=1, downsample=None, fused=False):
+    def __init__(self, cin, planes, stride=1, downsample=None, fused=False,
+                 fork=False):
         super().__init__()
         self.fused = fused
+        self.fork = fork and fused  # as in BasicBlock
         self.conv1 = conv1x1(cin, planes)
         self.conv2 = conv3x3(planes, planes, stride)
         self.conv3 = conv1x1(planes, planes * self.expansion)
@@ -80,11 +109,14 @@ class Bottleneck(nn.Module):
             self.relu = nn.ReLU(inplace=True)
 
     def forward(self, x):
-        identity = self.downsample(x) if self.downsample is not None else x
+        x, skip = _split(x)
+        identity = (self.downsample(skip) if self.downsample is not None
+                    else skip)
         if self.fused:
             out = self.bn1(self.conv1(x))
             out = self.bn2(self.conv2(out))
-            return self.bn3(self.conv3(out), residual=identity)
+            return _last_bn(self.bn3, self.conv3(out), identity,
+                            getattr(self, "fork", False))
         out = self.relu(self.bn1(self.conv1(x)))
         out = self.relu(self.bn2(self.conv2(out)))
         out = self.bn3(self.conv3(out))
@@ -99,9 +131,14 @@ class ResNet(nn.Module):
         num_classes: int = 1000,
         in_chans: int = 3,
         fused: bool = False,
+        fork_grads: bool = True,
     ):
         super().__init__()
         self.fused = fused
+        # fused models: every block whose output feeds another block hands
+        # it over as a (main, skip) pair (_last_bn).  Same math either way;
+        # False keeps autograd's own gradient add at each fork.
+        self.fork_grads = fork_grads and fused
         self.inplanes = 64
         self.conv1 = nn.Conv2d(in_chans, 64, 7, stride=2, padding=3, bias=False)
         if fused:
@@ -113,7 +150,8 @@ class ResNet(nn.Module):
         self.layer1 = self._make_layer(block, 64, layers[0])
         self.layer2 = self._make_layer(block, 128, layers[1], stride=2)
         self.layer3 = self._make_layer(block, 256, layers[2], stride=2)
-        self.layer4 = self._make_layer(block, 512, layers[3], stride=2)
+        self.layer4 = self._make_layer(block, 512, layers[3], stride=2,
+                                       fork_last=False)
         self.avgpool = nn.AdaptiveAvgPool2d(1)
         self.fc = nn.Linear(512 * block.expansion, num_classes)
         for m in self.modules():
@@ -121,7 +159,10 @@ class ResNet(nn.Module):
                 nn.init.kaiming_normal_(m.weight, mode="fan_out",
                                         nonlinearity="relu")
 
-    def _make_layer(self, block, planes, blocks, stride=1):
+    def _make_layer(self, block, planes, blocks, stride=1, fork_last=True):
+        # fork_last: the layer's last block feeds the next layer's first
+        fork = [self.fork_grads] * (blocks - 1) + [self.fork_grads
+                                                   and fork_last]
         downsample = None
         if stride != 1 or self.inplanes != planes * block.expansion:
             downsample = nn.Sequential(
@@ -129,10 +170,11 @@ class ResNet(nn.Module):
                 _norm(planes * block.expansion, self.fused),
             )
         layers = [block(self.inplanes, planes, stride, downsample,
-                        fused=self.fused)]
+                        fused=self.fused, fork=fork[0])]
         self.inplanes = planes * block.expansion
-        for _ in range(1, blocks):
-            layers.append(block(self.inplanes, planes, fused=self.fused))
+        for i in range(1, blocks):
+            layers.append(block(self.inplanes, planes, fused=self.fused,
+                                fork=fork[i]))
         return nn.Sequential(*layers)
 
     def _stem(self, x):
@@ -143,11 +185,14 @@ class ResNet(nn.Module):
 
     def forward_features(self, x):
         x = self._stem(x)
+        # a forking layer hands its (main, skip) pair to the next layer; the
+        # caller gets plain tensors (main: an extra consumer's gradient is
+        # summed there by autograd as before)
         c2 = self.layer1(x)
         c3 = self.layer2(c2)
         c4 = self.layer3(c3)
         c5 = self.layer4(c4)
-        return c2, c3, c4, c5
+        return _split(c2)[0], _split(c3)[0], _split(c4)[0], _split(c5)[0]
 
     def forward(self, x):
         _, _, _, c5 = self.forward_features(x)
@@ -155,9 +200,13 @@ class ResNet(nn.Module):
         return self.fc(out)
 
 
-def resnet18(num_classes: int = 1000, fused: bool = False) -> ResNet:
-    return ResNet(BasicBlock, [2, 2, 2, 2], num_classes, fused=fused)
+def resnet18(num_classes: int = 1000, fused: bool = False,
+             fork_grads: bool = True) -> ResNet:
+    return ResNet(BasicBlock, [2, 2, 2, 2], num_classes, fused=fused,
+                  fork_grads=fork_grads)
 
 
-def resnet50(num_classes: int = 1000, fused: bool = False) -> ResNet:
-    return ResNet(Bottleneck, [3, 4, 6, 3], num_classes, fused=fused)
+def resnet50(num_classes: int = 1000, fused: bool = False,
+             fork_grads: bool = True) -> ResNet:
+    return ResNet(Bottleneck, [3, 4, 6, 3], num_classes, fused=fused,
+                  fork_grads=fork_grads)

@@ -41,7 +41,30 @@ class SyncBatchNormActFunction(torch.autograd.Function):
         world_size: int,
         relu: bool,
         negative_slope: float = 0.0,
+        fork: bool = False,
     ):
+        """``fork=True`` returns the output twice — ``(y, y.detach())``, two
+        tensor objects over one storage, no copy — for a result that feeds
+        two consumers (a residual block's conv1 and its skip path).  Autograd
+        sums gradients per output edge, so two outputs are what lets
+        ``backward`` receive the two gradients UNSUMMED and read both inside
+        the reduce kernel instead of paying for an eager add (read 2A, write
+        1A) whose only reader is that kernel."""
+        ctx.fork = fork
+        y = SyncBatchNormActFunction._forward(
+            ctx, input, residual, weight, bias, running_mean, running_var,
+            eps, momentum, process_group, world_size, relu, negative_slope,
+        )
+        if not fork:
+            return y
+        # an unused output then arrives as None, not as a full-size zero fill
+        ctx.set_materialize_grads(False)
+        return y, y.detach()
+
+    @staticmethod
+    def _forward(ctx, input, residual, weight, bias, running_mean,
+                 running_var, eps, momentum, process_group, world_size, relu,
+                 negative_slope):
         ctx.negative_slope = negative_slope
         input = _contig(input)
         if residual is not None:
@@ -105,7 +128,11 @@ class SyncBatchNormActFunction(torch.autograd.Function):
         )
 
     @staticmethod
-    def backward(ctx, grad_output: torch.Tensor):
+    def backward(ctx, grad_output, grad_skip=None):
+        if grad_output is None:  # fork with only the second output used
+            grad_output, grad_skip = grad_skip, None
+        if grad_output is None:
+            return (None,) * 13
         if ctx.has_coefs:
             (input, residual, weight, bias, mean, invstd, count_sum,
              coefs) = ctx.saved_tensors
@@ -114,7 +141,29 @@ class SyncBatchNormActFunction(torch.autograd.Function):
                 ctx.saved_tensors
             )
             coefs = None
+        # Both gradients of a forked output: the two-stage GPU path hands
+        # them to the reduce kernel unsummed (grad_out2); every other path
+        # (small-plane kernel, CPU, empty-input rank) starts with the eager
+        # add autograd itself would have run.
+        fold = (
+            grad_skip is not None and input.is_cuda and input.numel() > 0
+            and not getattr(ctx, "local_fused", False)
+        )
+        # The fold needs gm (below).  gm holds the gated gradient rounded to
+        # the activation dtype: exact for none / relu (the gate passes or
+        # zeroes a value that already is one), but slope*g is not, so a leaky
+        # layer that would not have materialized gm anyway keeps the eager
+        # add and its fp32 gate.
+        if fold and ctx.relu and ctx.negative_slope != 0.0 and not (
+            residual is not None and ctx.needs_input_grad[1]
+        ):
+            fold = False
+        if grad_skip is not None and not fold:
+            grad_output = grad_output + grad_skip
+            grad_skip = None
         grad_output = _match_layout(grad_output, input)
+        if fold:
+            grad_skip = _match_layout(grad_skip, input)
         relu = ctx.relu
         slope = ctx.negative_slope
         process_group = ctx.process_group
@@ -141,7 +190,7 @@ class SyncBatchNormActFunction(torch.autograd.Function):
                 grad_res if need_res_g else None,
                 grad_weight if need_weight_g else None,
                 grad_bias if need_bias_g else None,
-                None, None, None, None, None, None, None, None,
+                None, None, None, None, None, None, None, None, None,
             )
 
         # Masked-grad materialization: when the residual branch needs its
@@ -149,7 +198,10 @@ class SyncBatchNormActFunction(torch.autograd.Function):
         # where z<=0) once; the elemt pass then reads gm instead of
         # (dy, residual) and gm itself IS the residual gradient -> one fewer
         # full-tensor read+write (8A -> 7A).
-        use_gm = (
+        # With both fork gradients (fold) gm is always written: the reduce
+        # kernel is the only place their sum exists, and the elemt pass must
+        # not read dy / dy2 again.
+        use_gm = fold or (
             relu and residual is not None and need_res_g and input.is_cuda
             and input.numel() > 0
         )
@@ -171,14 +223,14 @@ class SyncBatchNormActFunction(torch.autograd.Function):
                 torch.empty_like(grad_output) if need_res_g else None,
                 torch.zeros_like(weight) if need_weight_g else None,
                 torch.zeros_like(bias) if need_bias_g else None,
-                None, None, None, None, None, None, None, None,
+                None, None, None, None, None, None, None, None, None,
             )
         gm = torch.empty_like(grad_output) if use_gm else None
         sum_dy, sum_dy_xmu, grad_weight, grad_bias = (
             ops.batch_norm_backward_reduce_act(
                 grad_output, input, residual, mean, invstd, weight, bias,
                 relu, need_input_g, need_weight_g, need_bias_g, coefs, gm,
-                slope,
+                slope, grad_skip,
             )
         )
         grad_input = grad_res = None
@@ -200,7 +252,7 @@ class SyncBatchNormActFunction(torch.autograd.Function):
                     gm, input, None, mean, invstd, weight, bias,
                     sum_dy, sum_dy_xmu, count_sum, False, False, coefs,
                 )
-                grad_res = gm
+                grad_res = gm if need_res_g else None
             else:
                 grad_input, grad_res = ops.batch_norm_backward_elemt_act(
                     grad_output, input, residual, mean, invstd, weight, bias,
@@ -212,7 +264,7 @@ class SyncBatchNormActFunction(torch.autograd.Function):
             grad_res,
             grad_weight if need_weight_g else None,
             grad_bias if need_bias_g else None,
-            None, None, None, None, None, None, None, None,
+            None, None, None, None, None, None, None, None, None,
         )
 
 
@@ -241,7 +293,11 @@ class SyncBatchNormAct2d(SyncBatchNorm):
         return s
 
     def forward(self, input: torch.Tensor,
-                residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+                residual: Optional[torch.Tensor] = None, fork: bool = False):
+        """``fork=True`` returns the output as a ``(main, skip)`` pair of
+        tensors over one storage, for a result with two consumers: their
+        gradients then reach this layer's backward unsummed (see
+        SyncBatchNormActFunction.forward).  Train and eval mode alike."""
         self._check_input_dim(input)
         self._check_non_zero_input_channels(input)
         # default: modules pickled before negative_slope existed
@@ -258,8 +314,11 @@ class SyncBatchNormAct2d(SyncBatchNorm):
         )
 
         if not bn_training:
-            return _running_stats_forward(self, input, residual, self.relu,
-                                          slope)
+            # the frozen kernels take one gradient: both consumers hang off
+            # the same tensor and autograd sums for them, as ever
+            y = _running_stats_forward(self, input, residual, self.relu,
+                                       slope)
+            return (y, y) if fork else y
 
         process_group = None
         world_size = 1
@@ -272,4 +331,5 @@ class SyncBatchNormAct2d(SyncBatchNorm):
         return SyncBatchNormActFunction.apply(
             input, residual, self.weight, self.bias, running_mean, running_var,
             self.eps, factor, process_group, world_size, self.relu, slope,
+            fork,
         )

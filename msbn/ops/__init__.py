@@ -229,15 +229,22 @@ def batch_norm_elemt_act(input, residual, weight, bias, mean, invstd,
 def batch_norm_backward_reduce_act(grad_out, input, residual, mean, invstd,
                                    weight, bias, relu_mask, input_g, weight_g,
                                    bias_g, coefs=None, gm_out=None,
-                                   negative_slope: float = 0.0):
+                                   negative_slope: float = 0.0,
+                                   grad_out2=None):
+    """First pass of the fused BN backward.  ``grad_out2`` is the second
+    gradient of a forked output, delivered unsummed: the incoming gradient is
+    ``grad_out + grad_out2`` rounded to the input dtype once (the tensor an
+    eager add would have produced), read inside the reduce kernel instead of
+    in a pass of its own.  It requires ``gm_out``."""
     if input.is_cuda:
         return _require_hip().batch_norm_backward_reduce_act(
             grad_out, input, residual, mean, invstd, weight, bias, relu_mask,
             input_g, weight_g, bias_g, coefs, gm_out, negative_slope,
+            grad_out2,
         )
     return _ref.batch_norm_backward_reduce_act(
         grad_out, input, residual, mean, invstd, weight, bias, relu_mask,
-        input_g, weight_g, bias_g, gm_out, negative_slope,
+        input_g, weight_g, bias_g, gm_out, negative_slope, grad_out2,
     )
 
 
@@ -298,7 +305,8 @@ def launch_plan(kind: str, input: torch.Tensor, others=(), coefs=None) -> dict:
 
     ``kind`` / tensors (pass only what the op itself would dereference):
       ``"stats"``             input = x
-      ``"bwd_reduce"``        input = x, others = (grad_out, residual, gm_out)
+      ``"bwd_reduce"``        input = x, others = (grad_out, residual, gm_out,
+                                                   grad_out2)
       ``"elemt"``             input = x, others = (residual,), coefs
       ``"bwd_elemt"``         input = x, others = (grad_out, residual), coefs
       ``"frozen_bwd_elemt"``  input = grad_out, others = (x, residual), coefs

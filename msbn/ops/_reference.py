@@ -183,7 +183,12 @@ def _masked_grad(grad_out, input, residual, mean, invstd, weight, bias,
 def batch_norm_backward_reduce_act(
     grad_out, input, residual, mean, invstd, weight, bias, relu_mask,
     input_g, weight_g, bias_g, gm_out=None, negative_slope: float = 0.0,
+    grad_out2=None,
 ):
+    if grad_out2 is not None:
+        # the two gradients of a forked output: summed in the input dtype
+        # first (one rounding), as autograd's own accumulation would
+        grad_out = grad_out + grad_out2
     g = _masked_grad(grad_out, input, residual, mean, invstd, weight, bias,
                      relu_mask, negative_slope)
     if gm_out is not None:

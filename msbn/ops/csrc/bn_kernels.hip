@@ -521,9 +521,23 @@ __global__ void bn_elemt_nhwc(const T* __restrict__ x,
 // leaky: z>0 ? dy : slope*dy): the pre-activation
 // z = scale[c]*x + shift[c] (+ res) is recomputed in-kernel, so the fused
 // forward never has to store a mask or the pre-activation tensor.
+//
+// DY2: the layer's output forked (residual block: conv1 and the skip path)
+// and the two gradients arrive unsummed; the kernel reads both and folds
+// autograd's `dy + dy2` pass (read 2A, write 1A) into its own dy read.  The
+// fp32 sum is rounded to T ONCE before the gate, exactly what the eager
+// add<T> kernel stored (fp32 opmath, round-to-nearest-even), so gm, the
+// sums and everything downstream keep their bits.  Only instantiated with
+// GMOUT: the second pass then reads gm and never needs dy / dy2 again.
 // =====================================================================
-template <typename T, int V, int ACT, bool RES, bool GMOUT>
+template <typename T>
+__device__ __forceinline__ float fork_grad(T g1, T g2) {
+  return to_f(from_f<T>(to_f(g1) + to_f(g2)));
+}
+
+template <typename T, int V, int ACT, bool RES, bool GMOUT, bool DY2>
 __global__ void bn_bwd_reduce_partial_nchw(const T* __restrict__ dy,
+                                           const T* __restrict__ dy2,
                                            const T* __restrict__ x,
                                            const T* __restrict__ res,
                                            T* __restrict__ gm_out,
@@ -547,7 +561,9 @@ __global__ void bn_bwd_reduce_partial_nchw(const T* __restrict__ dy,
     const int64_t base = (n * C + c) * S;
     if (V == 1) {
       for (int64_t s = s0 + threadIdx.x; s < s1; s += blockDim.x) {
-        float g = to_f(nt_load1(&dy[base + s]));
+        float g = DY2 ? fork_grad(nt_load1(&dy[base + s]),
+                                  nt_load1(&dy2[base + s]))
+                      : to_f(nt_load1(&dy[base + s]));
         const float xv = to_f(nt_load1(&x[base + s]));
         if (ACT) {
           float z = sc * xv + sh;
@@ -566,11 +582,12 @@ __global__ void bn_bwd_reduce_partial_nchw(const T* __restrict__ dy,
            s += (int64_t)blockDim.x * V) {
         Pack<T, V> pg = nt_load<T, V>(&dy[base + s]);
         Pack<T, V> px = nt_load<T, V>(&x[base + s]);
-        Pack<T, V> pr, pm;
+        Pack<T, V> pg2, pr, pm;
+        if (DY2) pg2 = nt_load<T, V>(&dy2[base + s]);
         if (RES) pr = nt_load<T, V>(&res[base + s]);
 #pragma unroll
         for (int k = 0; k < V; ++k) {
-          float g = to_f(pg.v[k]);
+          float g = DY2 ? fork_grad(pg.v[k], pg2.v[k]) : to_f(pg.v[k]);
           const float xv = to_f(px.v[k]);
           if (ACT) {
             float z = sc * xv + sh;
@@ -600,9 +617,10 @@ __global__ void bn_bwd_reduce_partial_nchw(const T* __restrict__ dy,
   }
 }
 
-template <typename T, int ACT, bool RES, bool GMOUT>
+template <typename T, int ACT, bool RES, bool GMOUT, bool DY2>
 __global__ void bn_bwd_reduce_partial_nchw_flat(
-    const T* __restrict__ dy, const T* __restrict__ x,
+    const T* __restrict__ dy, const T* __restrict__ dy2,
+    const T* __restrict__ x,
     const T* __restrict__ res, T* __restrict__ gm_out,
     const float* __restrict__ mean,
     const float* __restrict__ scale, const float* __restrict__ shift,
@@ -620,7 +638,8 @@ __global__ void bn_bwd_reduce_partial_nchw_flat(
   for (int64_t p = p0 + threadIdx.x; p < p1; p += blockDim.x) {
     const int64_t n = p / S, s = p - n * S;
     const int64_t e = (n * C + c) * S + s;
-    float g = to_f(nt_load1(&dy[e]));
+    float g = DY2 ? fork_grad(nt_load1(&dy[e]), nt_load1(&dy2[e]))
+                  : to_f(nt_load1(&dy[e]));
     const float xv = to_f(nt_load1(&x[e]));
     if (ACT) {
       float z = sc * xv + sh;
@@ -645,8 +664,9 @@ __global__ void bn_bwd_reduce_partial_nchw_flat(
   }
 }
 
-template <typename T, int V, int ACT, bool RES, bool GMOUT>
+template <typename T, int V, int ACT, bool RES, bool GMOUT, bool DY2>
 __global__ void bn_bwd_reduce_partial_nhwc(const T* __restrict__ dy,
+                                           const T* __restrict__ dy2,
                                            const T* __restrict__ x,
                                            const T* __restrict__ res,
                                            T* __restrict__ gm_out,
@@ -683,11 +703,12 @@ __global__ void bn_bwd_reduce_partial_nhwc(const T* __restrict__ dy,
     for (int64_t r = r0 + rowoff; r < r1; r += rpi) {
       Pack<T, V> pg = nt_load<T, V>(&dy[r * C + c]);
       Pack<T, V> px = nt_load<T, V>(&x[r * C + c]);
-      Pack<T, V> pr, pm;
+      Pack<T, V> pg2, pr, pm;
+      if (DY2) pg2 = nt_load<T, V>(&dy2[r * C + c]);
       if (RES) pr = nt_load<T, V>(&res[r * C + c]);
 #pragma unroll
       for (int k = 0; k < V; ++k) {
-        float g = to_f(pg.v[k]);
+        float g = DY2 ? fork_grad(pg.v[k], pg2.v[k]) : to_f(pg.v[k]);
         const float xv = to_f(px.v[k]);
         if (ACT) {
           float z = scv[k] * xv + shv[k];
@@ -1870,7 +1891,8 @@ batch_norm_backward_reduce_act(
     const at::Tensor& invstd, const c10::optional<at::Tensor>& weight,
     const c10::optional<at::Tensor>& bias, bool relu_mask, bool input_g,
     bool weight_g, bool bias_g, const c10::optional<at::Tensor>& coefs_in,
-    const c10::optional<at::Tensor>& gm_out, double negative_slope) {
+    const c10::optional<at::Tensor>& gm_out, double negative_slope,
+    const c10::optional<at::Tensor>& grad_out2) {
   const Layout L = get_layout(input);
   const float slope = (float)negative_slope;
   const int act = act_mode(relu_mask, slope);
@@ -1895,6 +1917,15 @@ batch_norm_backward_reduce_act(
   TORCH_CHECK(grad_out.sizes() == input.sizes() &&
                   grad_out.strides() == input.strides(),
               "grad_out must match input shape and layout");
+  const bool has_dy2 = grad_out2.has_value();
+  if (has_dy2) {
+    TORCH_CHECK(want_gm, "grad_out2 requires gm_out");
+    TORCH_CHECK(grad_out2->sizes() == input.sizes() &&
+                    grad_out2->strides() == input.strides() &&
+                    grad_out2->scalar_type() == input.scalar_type() &&
+                    grad_out2->device() == input.device(),
+                "grad_out2 must match input shape/strides/dtype");
+  }
   TORCH_CHECK(!residual.has_value() ||
                   (residual->sizes() == input.sizes() &&
                    residual->strides() == input.strides()),
@@ -1934,10 +1965,13 @@ batch_norm_backward_reduce_act(
                 : nullptr;
     native_t* gm =
         want_gm ? reinterpret_cast<native_t*>(gm_out->data_ptr()) : nullptr;
+    const native_t* dy2 =
+        has_dy2 ? reinterpret_cast<const native_t*>(grad_out2->data_ptr())
+                : nullptr;
     constexpr int VMAX = 16 / (int)sizeof(native_t);
-    // every pointer the partial kernel dereferences, gm_out included
+    // every pointer the partial kernel dereferences, gm_out / dy2 included
     const ReducePlan plan =
-        plan_reduce(L, (int)sizeof(native_t), {x, dy, res, gm});
+        plan_reduce(L, (int)sizeof(native_t), {x, dy, res, gm, dy2});
     const int v = plan.v;
     const int nchunks = plan.nchunks;
     at::Tensor ws = at::empty({(int64_t)nchunks * L.C * 2},
@@ -1945,34 +1979,49 @@ batch_norm_backward_reduce_act(
     MSBN_DISPATCH_ACT(act, ACT_, [&] {
       MSBN_DISPATCH_BOOL(has_res, RES_, [&] {
         MSBN_DISPATCH_BOOL(want_gm, GM_, [&] {
-        if (!L.nhwc) {
-          if (plan.path == RedPath::NchwFlat) {
-            const auto& g = plan.flat;
-            hipLaunchKernelGGL(
-                (bn_bwd_reduce_partial_nchw_flat<native_t, ACT_, RES_, GM_>),
-                g.grid, dim3(MSBN_BLOCK), 0, stream, dy, x, res, gm,
-                mean.data_ptr<float>(), scale, shift, ws.data_ptr<double>(),
-                L.N, L.C, L.S, g.chunk_len, slope);
+          // DY2 exists only with GMOUT (has_dy2 implies want_gm, checked
+          // above): 3 kernels per (T, V, ACT, RES), not 4
+          auto launch = [&](auto dy2_c) {
+            constexpr bool DY2_ = decltype(dy2_c)::value && GM_;
+            if (!L.nhwc) {
+              if (plan.path == RedPath::NchwFlat) {
+                const auto& g = plan.flat;
+                hipLaunchKernelGGL(
+                    (bn_bwd_reduce_partial_nchw_flat<native_t, ACT_, RES_,
+                                                     GM_, DY2_>),
+                    g.grid, dim3(MSBN_BLOCK), 0, stream, dy, dy2, x, res, gm,
+                    mean.data_ptr<float>(), scale, shift,
+                    ws.data_ptr<double>(), L.N, L.C, L.S, g.chunk_len, slope);
+              } else {
+                const auto& g = plan.nchw;
+                MSBN_DISPATCH_V(v, VMAX, [&] {
+                  hipLaunchKernelGGL(
+                      (bn_bwd_reduce_partial_nchw<native_t, VV, ACT_, RES_,
+                                                  GM_, DY2_>),
+                      g.grid, dim3(MSBN_BLOCK), 0, stream, dy, dy2, x, res,
+                      gm, mean.data_ptr<float>(), scale, shift,
+                      ws.data_ptr<double>(), L.N, L.C, L.S, g.chunkN,
+                      g.chunkS, slope);
+                });
+              }
+            } else {
+              const auto& g = plan.nhwc;
+              MSBN_DISPATCH_V(v, VMAX, [&] {
+                hipLaunchKernelGGL(
+                    (bn_bwd_reduce_partial_nhwc<native_t, VV, ACT_, RES_, GM_,
+                                                DY2_>),
+                    g.grid, dim3(MSBN_BLOCK), 0, stream, dy, dy2, x, res, gm,
+                    mean.data_ptr<float>(), scale, shift,
+                    ws.data_ptr<double>(), L.rows, L.C, g.chunk_rows, g.lpr,
+                    slope);
+              });
+            }
+          };
+          if (has_dy2) {
+            launch(std::true_type{});
           } else {
-            const auto& g = plan.nchw;
-            MSBN_DISPATCH_V(v, VMAX, [&] {
-              hipLaunchKernelGGL(
-                  (bn_bwd_reduce_partial_nchw<native_t, VV, ACT_, RES_, GM_>),
-                  g.grid, dim3(MSBN_BLOCK), 0, stream, dy, x, res, gm,
-                  mean.data_ptr<float>(), scale, shift, ws.data_ptr<double>(),
-                  L.N, L.C, L.S, g.chunkN, g.chunkS, slope);
-            });
+            launch(std::false_type{});
           }
-        } else {
-          const auto& g = plan.nhwc;
-          MSBN_DISPATCH_V(v, VMAX, [&] {
-            hipLaunchKernelGGL(
-                (bn_bwd_reduce_partial_nhwc<native_t, VV, ACT_, RES_, GM_>),
-                g.grid, dim3(MSBN_BLOCK), 0, stream, dy, x, res, gm,
-                mean.data_ptr<float>(), scale, shift, ws.data_ptr<double>(),
-                L.rows, L.C, g.chunk_rows, g.lpr, slope);
-          });
-        }
         });
       });
     });
@@ -2001,7 +2050,8 @@ batch_norm_backward_reduce(const at::Tensor& grad_out, const at::Tensor& input,
   return batch_norm_backward_reduce_act(grad_out, input, c10::nullopt, mean,
                                         invstd, weight, c10::nullopt, false,
                                         input_g, weight_g, bias_g,
-                                        c10::nullopt, c10::nullopt, 0.0);
+                                        c10::nullopt, c10::nullopt, 0.0,
+                                        c10::nullopt);
 }
 
 std::tuple<at::Tensor, at::Tensor> batch_norm_backward_elemt_act(

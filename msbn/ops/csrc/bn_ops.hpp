@@ -99,6 +99,11 @@ at::Tensor batch_norm_elemt_act(const at::Tensor& input,
                                 const c10::optional<at::Tensor>& coefs_in,
                                 double negative_slope);
 
+// grad_out2: second gradient of a forked output (residual block: conv1 and
+// the skip path), delivered unsummed.  The kernel uses
+// round_T(grad_out + grad_out2) as the incoming gradient — bit for bit the
+// tensor an eager add would have stored — without that add's pass over
+// memory.  Requires gm_out (the second pass then reads gm alone).
 std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor>
 batch_norm_backward_reduce_act(
     const at::Tensor& grad_out, const at::Tensor& input,
@@ -106,7 +111,8 @@ batch_norm_backward_reduce_act(
     const at::Tensor& invstd, const c10::optional<at::Tensor>& weight,
     const c10::optional<at::Tensor>& bias, bool relu_mask, bool input_g,
     bool weight_g, bool bias_g, const c10::optional<at::Tensor>& coefs_in,
-    const c10::optional<at::Tensor>& gm_out, double negative_slope);
+    const c10::optional<at::Tensor>& gm_out, double negative_slope,
+    const c10::optional<at::Tensor>& grad_out2);
 
 // ---- frozen path (normalize with running stats, autograd on) --------------
 // One launch: (running_mean, running_var, eps, weight?, bias?) -> packed fp32
@@ -173,7 +179,8 @@ std::tuple<at::Tensor, at::Tensor> batch_norm_backward_elemt_act(
 // Which kernel path a call would take and how far its loops run, decided by
 // the same host code the ops launch with.  kind / tensors:
 //   "stats"            input = x
-//   "bwd_reduce"       input = x,        others = {grad_out, residual, gm_out}
+//   "bwd_reduce"       input = x,        others = {grad_out, residual, gm_out,
+//                                              grad_out2}
 //   "elemt"            input = x,        others = {residual},  coefs
 //   "bwd_elemt"        input = x,        others = {grad_out, residual}, coefs
 //   "frozen_bwd_elemt" input = grad_out, others = {x, residual}, coefs

@@ -54,7 +54,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("invstd"), py::arg("weight"), py::arg("bias"),
         py::arg("relu_mask"), py::arg("input_g"), py::arg("weight_g"),
         py::arg("bias_g"), py::arg("coefs") = py::none(),
-        py::arg("gm_out") = py::none(), py::arg("negative_slope") = 0.0);
+        py::arg("gm_out") = py::none(), py::arg("negative_slope") = 0.0,
+        py::arg("grad_out2") = py::none());
   m.def("batch_norm_backward_elemt_act", &msbn::batch_norm_backward_elemt_act,
         py::arg("grad_out"), py::arg("input"), py::arg("residual"),
         py::arg("mean"), py::arg("invstd"), py::arg("weight"), py::arg("bias"),

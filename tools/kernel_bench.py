@@ -77,10 +77,13 @@ def main():
         x = torch.randn(N, C, H, W, device=dev, dtype=dt)
         dy = torch.randn_like(x)
         res = torch.randn_like(x)
+        dy2 = torch.randn_like(x)
         if cl:
             x = x.to(memory_format=torch.channels_last)
             dy = dy.to(memory_format=torch.channels_last)
             res = res.to(memory_format=torch.channels_last)
+            dy2 = dy2.to(memory_format=torch.channels_last)
+        gm = torch.empty_like(x)
         w = torch.randn(C, device=dev).abs() + 0.1
         b = torch.randn(C, device=dev)
         mean, invstd = ops.batch_norm_stats(x, 1e-5)
@@ -109,6 +112,20 @@ def main():
                 lambda: ops.batch_norm_backward_elemt(dy, x, mean, invstd, w,
                                                       sum_dy, sum_dy_xmu, cnt),
                 3 * nbytes),
+            # the residual block's closing BN: reads dy, x, res, writes gm
+            "bwd_reduce+res+gm": (
+                lambda: ops.batch_norm_backward_reduce_act(
+                    dy, x, res, mean, invstd, w, b, True, True, True, True,
+                    coefs, gm),
+                4 * nbytes),
+            # ... with the fork's second gradient read in the same pass,
+            # against the eager add (read 2, write 1) it replaces
+            "bwd_reduce+res+gm+dy2": (
+                lambda: ops.batch_norm_backward_reduce_act(
+                    dy, x, res, mean, invstd, w, b, True, True, True, True,
+                    coefs, gm, 0.0, dy2),
+                5 * nbytes),
+            "add(dy,dy2)": (lambda: torch.add(dy, dy2), 3 * nbytes),
         }
         for name, (fn, byt) in cases.items():
             us = bench(fn, args.iters)
@@ -119,9 +136,9 @@ def main():
     if args.json:
         print(json.dumps(rows))
     else:
-        print(f"{'shape':>18} {'kernel':>16} {'us':>9} {'GB/s':>8}")
+        print(f"{'shape':>18} {'kernel':>22} {'us':>9} {'GB/s':>8}")
         for r in rows:
-            print(f"{r['shape']:>18} {r['kernel']:>16} {r['us']:>9} "
+            print(f"{r['shape']:>18} {r['kernel']:>22} {r['us']:>9} "
                   f"{r['GBps']:>8}")
 
 
