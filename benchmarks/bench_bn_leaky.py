@@ -5,11 +5,17 @@ epilogue at the DCGAN discriminator's three BN stages (batch 128).
     python benchmarks/bench_bn_leaky.py [--iters 10 --rounds 5]
 
 Training-mode BatchNorm (batch statistics, world size 1) followed by
-LeakyReLU(0.2), gradients for the input and the affine parameters.  Three
+LeakyReLU(0.2), gradients for the input and the affine parameters.  Four
 arms, alternated round-robin inside ONE process after every shape has been
 warmed (so clocks / allocator state are shared):
 
     fused     msbn.nn.SyncBatchNormAct2d(relu=True, negative_slope=0.2)
+    inplace   the same module with inplace=True: y overwrites x, the
+              backward runs from y (always the two-stage kernels; the fused
+              arm takes the single-launch small-plane kernels where they
+              apply).  Its input is a non-leaf tensor over a fixed buffer
+              (no copy is timed), so each iteration normalises the previous
+              iteration's output: same bytes, same kernels, other values
     composed  msbn.nn.SyncBatchNorm + nn.LeakyReLU(0.2, inplace=True): what
               the discriminator ran before the leaky epilogue
     torch     torch.nn.BatchNorm2d + nn.LeakyReLU(0.2, inplace=True); fp32
@@ -40,7 +46,7 @@ import msbn
 # (N, C, H, W): the discriminator's BN inputs at batch 128, 64x64 images
 SHAPES = [(128, 128, 32, 32), (128, 256, 16, 16), (128, 512, 8, 8)]
 CONFIGS = [("fp32", torch.float32, False), ("bf16", torch.bfloat16, True)]
-ARMS = ["fused", "composed", "torch"]
+ARMS = ["fused", "inplace", "composed", "torch"]
 SLOPE = 0.2
 
 
@@ -55,9 +61,25 @@ def traffic_bytes(numel: int, itemsize: int, arm: str) -> int:
 
     fused = 8A: the activation rides in the BN normalize / reduce / elemt
     kernels (the gate is recomputed from x).  composed / torch = 13A.
+    inplace = 8A as well: stats read x, normalize read x + write y over it
+    (3A); reduce read dy, y (2A); elemt read dy, y, write dx (3A).
     """
     a = numel * itemsize
-    return (8 if arm == "fused" else 13) * a
+    return (8 if arm in ("fused", "inplace") else 13) * a
+
+
+class _Fresh(torch.autograd.Function):
+    """A non-leaf tensor that requires grad over a fixed buffer, at no
+    memory traffic: what an in-place layer may overwrite.  ``knob`` only
+    carries requires_grad; the incoming dx is dropped."""
+
+    @staticmethod
+    def forward(ctx, knob, buf):
+        return buf.detach()
+
+    @staticmethod
+    def backward(ctx, grad):
+        return torch.zeros((), device=grad.device), None
 
 
 def main():
@@ -103,6 +125,14 @@ def main():
             leaves = [x] + list(m.parameters())
             fns[arm] = (lambda m=m, leaves=leaves:
                         torch.autograd.grad(m(x), leaves, dy))
+        ip = msbn.nn.SyncBatchNormAct2d(C, relu=True, negative_slope=SLOPE,
+                                        inplace=True).to(dev).train()
+        buf = rnd()
+        knob = torch.zeros((), device=dev, requires_grad=True)
+        ip_leaves = [knob] + list(ip.parameters())
+        fns["inplace"] = (lambda: torch.autograd.grad(
+            ip(_Fresh.apply(knob, buf)), ip_leaves, dy))
+        fns = {arm: fns[arm] for arm in ARMS if arm in fns}
         return fns, x.numel(), x.element_size()
 
     # warm every shape / config / arm before any timing
@@ -161,7 +191,7 @@ def main():
                   "the three discriminator stages",
         "unit": "ms",
         "fp32_nchw": {a: total(a, "fp32") for a in ARMS},
-        "bf16_channels_last": {a: total(a, "bf16") for a in ARMS[:2]},
+        "bf16_channels_last": {a: total(a, "bf16") for a in ARMS[:3]},
     }))
 
 

@@ -32,6 +32,10 @@ def main():
     p.add_argument("--no-fused-d", action="store_true",
                    help="keep the discriminator's BN + LeakyReLU pairs "
                         "unfused (A/B line for the fused leaky epilogue)")
+    p.add_argument("--inplace-d", action="store_true",
+                   help="fuse the discriminator's BN + LeakyReLU pairs into "
+                        "in-place modules (y overwrites x, backward from y: "
+                        "one activation tensor less per BN layer)")
     p.add_argument("--benchmark", action="store_true",
                    help="MIOpen conv autotune (uses/extends the in-tree "
                         "miopen_db find-db)")
@@ -92,7 +96,7 @@ def main():
             G = fuse_bn_act(msbn.convert_sync_batchnorm(msbn.models.Generator())).to(device)
             D = msbn.convert_sync_batchnorm(msbn.models.Discriminator())
             if not args.no_fused_d:
-                D = fuse_bn_act(D)
+                D = fuse_bn_act(D, inplace=args.inplace_d)
             D = D.to(device)
             if world > 1:
                 G = msbn.parallel.DistributedDataParallel(
@@ -156,6 +160,7 @@ def main():
         dist.barrier()
     if use_cuda:
         torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
     t0 = time.perf_counter()
     if graph is not None:
         for _ in range(args.steps):
@@ -191,7 +196,12 @@ def main():
                        "parallelism": f"dp{world}",
                        "hip_graph": graph is not None,
                        "impl": "stock" if args.stock else "msbn",
-                       "fused_d": not (args.stock or args.no_fused_d)},
+                       "fused_d": not (args.stock or args.no_fused_d),
+                       "inplace_d": bool(args.inplace_d) and not (
+                           args.stock or args.no_fused_d)},
+            # peak of the timed steps on this rank (warm-up excluded)
+            "max_memory_allocated": (torch.cuda.max_memory_allocated()
+                                     if use_cuda else None),
         }))
     if world > 1:
         dist.destroy_process_group()

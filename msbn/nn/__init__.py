@@ -6,7 +6,11 @@ from msbn.nn.batchnorm import (  # noqa: F401
     convert_sync_batchnorm,
 )
 from msbn.nn.functions import SyncBatchNormFunction  # noqa: F401
-from msbn.nn.fused import SyncBatchNormAct2d, SyncBatchNormActFunction  # noqa: F401
+from msbn.nn.fused import (  # noqa: F401
+    InPlaceSyncBatchNormActFunction,
+    SyncBatchNormAct2d,
+    SyncBatchNormActFunction,
+)
 from msbn.nn.frozen import (  # noqa: F401
     FrozenBatchNorm2d,
     FrozenBatchNormActFunction,
@@ -25,5 +29,6 @@ __all__ = [
     "convert_sync_batchnorm",
     "SyncBatchNormFunction",
     "SyncBatchNormAct2d",
+    "InPlaceSyncBatchNormActFunction",
     "fuse_bn_act",
 ]

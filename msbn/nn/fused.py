@@ -268,6 +268,125 @@ class SyncBatchNormActFunction(torch.autograd.Function):
         )
 
 
+class InPlaceSyncBatchNormActFunction(torch.autograd.Function):
+    """In-Place Activated SyncBatchNorm (Rota Bulo et al., 2018): the output
+    ``y = act(bn(x))`` is written over ``x`` and the backward works from ``y``
+    alone, so the layer keeps no activation-sized tensor of its own (the next
+    conv saves ``y`` anyway).  ``act`` is the identity or LeakyReLU with
+    ``negative_slope > 0``; statistics, their sync and the running update are
+    those of SyncBatchNormActFunction.  Always the two-stage kernels."""
+
+    @staticmethod
+    def forward(
+        ctx,
+        input: torch.Tensor,
+        weight: torch.Tensor,
+        bias: torch.Tensor,
+        running_mean: Optional[torch.Tensor],
+        running_var: Optional[torch.Tensor],
+        eps: float,
+        momentum: float,
+        process_group,
+        world_size: int,
+        act: bool,
+        negative_slope: float = 0.0,
+    ):
+        if act and not negative_slope > 0.0:
+            raise ValueError(
+                "in-place BN needs an invertible activation: identity, or "
+                "LeakyReLU with negative_slope > 0"
+            )
+        if _contig(input) is not input:
+            raise ValueError(
+                "in-place BN needs a dense NCHW or channels-last input; a "
+                "copy would leave the caller's tensor unwritten"
+            )
+        weight = weight.contiguous()
+        bias = bias.contiguous()
+        use_sync = world_size > 1 or (
+            process_group is not None and _force_sync()
+        )
+        # the statistics are read before the overwrite (same stream)
+        mean, invstd, count_sum, coefs = compute_sync_stats(
+            input, eps, momentum, running_mean, running_var,
+            process_group, world_size, weight, bias, want_coefs=True,
+        )
+        if input.numel() > 0:
+            ops.batch_norm_elemt_act_(
+                input, weight, bias, mean, invstd, act, coefs, negative_slope
+            )
+        ctx.mark_dirty(input)
+        ctx.has_coefs = coefs is not None
+        saved = (input, weight, bias, mean, invstd, count_sum)
+        ctx.save_for_backward(*(saved + ((coefs,) if ctx.has_coefs else ())))
+        ctx.act = act
+        ctx.negative_slope = negative_slope
+        ctx.process_group = process_group
+        ctx.world_size = world_size
+        ctx.use_sync = use_sync
+        return input
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        saved = ctx.saved_tensors
+        y, weight, bias, mean, invstd, count_sum = saved[:6]
+        coefs = saved[6] if ctx.has_coefs else None
+        grad_output = _match_layout(grad_output, y)
+        act, slope = ctx.act, ctx.negative_slope
+        process_group = ctx.process_group
+        use_sync = ctx.use_sync
+        need_input_g, need_weight_g, need_bias_g = ctx.needs_input_grad[:3]
+        C = int(y.shape[1])
+
+        if y.numel() == 0:
+            # empty-input rank (join): contribute zeros, keep peers unblocked
+            if use_sync and need_input_g:
+                combined = torch.zeros(2 * C, dtype=torch.float32,
+                                       device=grad_output.device)
+                from msbn.utils import debug as _dbg
+                if _dbg.enabled():  # peers verify; skipping would hang them
+                    _dbg.verify_collective("syncbn.bwd.all_reduce", combined,
+                                           process_group)
+                dist.all_reduce(combined, dist.ReduceOp.SUM,
+                                group=process_group)
+            return (
+                torch.empty_like(grad_output) if need_input_g else None,
+                torch.zeros_like(weight) if need_weight_g else None,
+                torch.zeros_like(bias) if need_bias_g else None,
+                None, None, None, None, None, None, None, None,
+            )
+        sum_dy, sum_dy_xmu, grad_weight, grad_bias = (
+            ops.batch_norm_backward_reduce_inplace(
+                grad_output, y, invstd, weight, bias, act, need_input_g,
+                need_weight_g, need_bias_g, coefs, slope,
+            )
+        )
+        grad_input = None
+        if need_input_g:
+            if use_sync:
+                combined, copied = _combined_view(sum_dy, sum_dy_xmu, C)
+                from msbn.utils import debug as _dbg
+                if _dbg.enabled():
+                    _dbg.verify_collective("syncbn.bwd.all_reduce",
+                                           combined, process_group)
+                dist.all_reduce(combined, dist.ReduceOp.SUM, group=process_group)
+                from msbn.utils.logging import comm_log
+                comm_log.record("all_reduce", combined.numel() * 4,
+                                f"syncbn bwd C={C}")
+                if copied:
+                    sum_dy, sum_dy_xmu = combined[:C], combined[C:]
+            grad_input = ops.batch_norm_backward_elemt_inplace(
+                grad_output, y, mean, invstd, weight, bias, sum_dy,
+                sum_dy_xmu, count_sum, act, coefs, slope,
+            )
+        return (
+            grad_input,
+            grad_weight if need_weight_g else None,
+            grad_bias if need_bias_g else None,
+            None, None, None, None, None, None, None, None,
+        )
+
+
 class SyncBatchNormAct2d(SyncBatchNorm):
     """SyncBatchNorm with a fused (optional residual-add +) ReLU epilogue.
 
@@ -275,21 +394,55 @@ class SyncBatchNormAct2d(SyncBatchNorm):
     ``relu=True, negative_slope=s`` makes the activation LeakyReLU(s):
     leaky_relu(bn(x) + residual, s).  The slope is a hyper-parameter, not
     state: state-dict keys are those of SyncBatchNorm.
+
+    ``inplace=True`` (In-Place Activated BatchNorm) writes the output over
+    the input in training mode and runs the backward from the output, so the
+    layer keeps no activation-sized tensor alive: one activation tensor less
+    per layer, at the byte traffic of the out-of-place path.  It needs
+    ``affine=True`` and an invertible activation (``relu=False``, or
+    ``relu=True`` with ``negative_slope > 0``; plain ReLU is rejected), and
+    takes neither ``residual`` nor ``fork``.  Two preconditions the kernels
+    cannot check:
+
+    * ``weight != 0`` in every channel (the backward divides by
+      ``weight*invstd``): a zero-initialised last BN of a residual block is
+      incompatible; such a channel's gradients are finite but wrong.
+    * the input must not be needed by its producer's backward (autograd's
+      version counter raises if it is); conv outputs are fine.
+
+    In-place layers always take the two-stage kernels (a known cost for
+    planes <= 16K elements, where the out-of-place path has single-launch
+    kernels).  In eval mode an ``inplace=True`` module takes the ordinary
+    out-of-place running-statistics route, which saves nothing input-sized
+    beyond what the gate needs.  State-dict keys are unchanged.
     """
 
     def __init__(self, num_features, eps=1e-5, momentum=0.1, affine=True,
                  track_running_stats=True, process_group=None, device=None,
-                 dtype=None, relu: bool = True, negative_slope: float = 0.0):
+                 dtype=None, relu: bool = True, negative_slope: float = 0.0,
+                 inplace: bool = False):
         super().__init__(num_features, eps, momentum, affine,
                          track_running_stats, process_group, device, dtype)
         self.relu = relu
         self.negative_slope = _check_negative_slope(relu, negative_slope)
+        if inplace:
+            if not affine:
+                raise ValueError("inplace=True requires affine=True")
+            if relu and not self.negative_slope > 0.0:
+                raise ValueError(
+                    "inplace=True needs an invertible activation: "
+                    "relu=False, or relu=True with negative_slope > 0 "
+                    "(plain ReLU cannot be inverted)"
+                )
+        self.inplace = bool(inplace)
 
     def extra_repr(self):
         s = super().extra_repr()
         slope = getattr(self, "negative_slope", 0.0)
         if slope != 0.0:
             s += f", negative_slope={slope}"
+        if getattr(self, "inplace", False):
+            s += ", inplace=True"
         return s
 
     def forward(self, input: torch.Tensor,
@@ -302,6 +455,13 @@ class SyncBatchNormAct2d(SyncBatchNorm):
         self._check_non_zero_input_channels(input)
         # default: modules pickled before negative_slope existed
         slope = getattr(self, "negative_slope", 0.0)
+        # likewise for inplace
+        inplace = getattr(self, "inplace", False)
+        if inplace and (residual is not None or fork):
+            raise ValueError(
+                "an inplace=True SyncBatchNormAct2d takes neither a residual "
+                "nor fork=True"
+            )
 
         bn_training = self.training or (
             self.running_mean is None and self.running_var is None
@@ -328,6 +488,11 @@ class SyncBatchNormAct2d(SyncBatchNorm):
 
         running_mean = self.running_mean if self.track_running_stats else None
         running_var = self.running_var if self.track_running_stats else None
+        if inplace:
+            return InPlaceSyncBatchNormActFunction.apply(
+                input, self.weight, self.bias, running_mean, running_var,
+                self.eps, factor, process_group, world_size, self.relu, slope,
+            )
         return SyncBatchNormActFunction.apply(
             input, residual, self.weight, self.bias, running_mean, running_var,
             self.eps, factor, process_group, world_size, self.relu, slope,

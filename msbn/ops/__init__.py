@@ -265,6 +265,63 @@ def batch_norm_backward_elemt_act(grad_out, input, residual, mean, invstd,
     )
 
 
+def batch_norm_elemt_act_(input, weight, bias, mean, invstd, act: bool,
+                          coefs=None, negative_slope: float = 0.0):
+    """In place: ``input <- act(input*scale + shift)``; returns ``input``.
+    Bit-identical to ``batch_norm_elemt_act`` on a copy.  ``act`` needs
+    ``negative_slope > 0`` (LeakyReLU); ``act=False`` is the identity.  The
+    backward of a layer run this way works from the stored output:
+    ``batch_norm_backward_reduce_inplace`` /
+    ``batch_norm_backward_elemt_inplace``."""
+    if input.is_cuda:
+        _require_hip().batch_norm_elemt_act_(
+            input, weight, bias, mean, invstd, act, coefs, negative_slope
+        )
+        return input
+    return _ref.batch_norm_elemt_act_(
+        input, weight, bias, mean, invstd, act, negative_slope
+    )
+
+
+def batch_norm_backward_reduce_inplace(grad_out, output, invstd, weight, bias,
+                                       act: bool, input_g, weight_g, bias_g,
+                                       coefs=None,
+                                       negative_slope: float = 0.0):
+    """First backward pass from the stored OUTPUT ``y`` of an in-place layer:
+    the gate is ``sign(y)``, the pre-activation ``z = y > 0 ? y : y/slope``
+    and ``x - mean = (z - bias)/scale``.  Returns ``(sum_dy, sum_dy_xmu,
+    grad_weight, grad_bias)`` with the meaning (and, on the GPU, the one
+    ``[2C]`` buffer) of ``batch_norm_backward_reduce_act``.  Requires
+    ``weight*invstd != 0`` in every channel."""
+    if output.is_cuda:
+        return _require_hip().batch_norm_backward_reduce_inplace(
+            grad_out, output, invstd, weight, bias, act, input_g, weight_g,
+            bias_g, coefs, negative_slope,
+        )
+    return _ref.batch_norm_backward_reduce_inplace(
+        grad_out, output, invstd, weight, bias, act, input_g, weight_g,
+        bias_g, negative_slope,
+    )
+
+
+def batch_norm_backward_elemt_inplace(grad_out, output, mean, invstd, weight,
+                                      bias, sum_dy, sum_dy_xmu, count,
+                                      act: bool, coefs=None,
+                                      negative_slope: float = 0.0):
+    """Second backward pass from the stored output ``y``:
+    ``dx = a*g + (b/scale)*z + (d - b*shift/scale)`` with ``g`` / ``z``
+    recovered from ``y`` as in ``batch_norm_backward_reduce_inplace``."""
+    if output.is_cuda:
+        return _require_hip().batch_norm_backward_elemt_inplace(
+            grad_out, output, mean, invstd, weight, bias, sum_dy, sum_dy_xmu,
+            count, act, coefs, negative_slope,
+        )
+    return _ref.batch_norm_backward_elemt_inplace(
+        grad_out, output, mean, invstd, weight, bias, sum_dy, sum_dy_xmu,
+        count, act, negative_slope,
+    )
+
+
 def bn_frozen_coefs(running_mean, running_var, eps: float, weight, bias):
     """Packed fp32 [scale(C) | shift(C)] from FIXED running statistics in one
     launch: scale = weight*rsqrt(running_var+eps), shift = bias -
@@ -311,6 +368,9 @@ def launch_plan(kind: str, input: torch.Tensor, others=(), coefs=None) -> dict:
       ``"bwd_elemt"``         input = x, others = (grad_out, residual), coefs
       ``"frozen_bwd_elemt"``  input = grad_out, others = (x, residual), coefs
       ``"fused_local"``       input = x, others = (residual,)
+      ``"elemt_inplace"``       input = x, coefs
+      ``"bwd_reduce_inplace"``  input = y, others = (grad_out,)
+      ``"bwd_elemt_inplace"``   input = y, others = (grad_out,)
     ``None`` entries of ``others`` are absent tensors.
 
     Returns a dict with ``path`` (``"nchw_vec"``, ``"nchw_flat"``, ``"nhwc"``,
@@ -331,6 +391,9 @@ __all__ = [
     "launch_plan",
     "bn_frozen_coefs",
     "batch_norm_frozen_backward_elemt",
+    "batch_norm_elemt_act_",
+    "batch_norm_backward_reduce_inplace",
+    "batch_norm_backward_elemt_inplace",
     "batch_norm_elemt_act",
     "bn_make_coefs",
     "batch_norm_backward_reduce_act",

@@ -211,6 +211,104 @@ def batch_norm_backward_elemt_act(
     return dx, dres
 
 
+# ---- in-place activated path ----------------------------------------------
+# fp32 throughout, in the kernels' order of operations: these are the CPU
+# execution path of the in-place ops, and they really overwrite ``input``.
+
+def _check_invertible(act: bool, negative_slope: float, name: str):
+    if act and not negative_slope > 0.0:
+        raise RuntimeError(
+            f"{name}: the in-place path needs an invertible activation "
+            "(identity, or LeakyReLU with negative_slope > 0); got "
+            f"negative_slope={negative_slope}"
+        )
+
+
+def _slope32(negative_slope: float):
+    s = torch.tensor(negative_slope, dtype=torch.float32)
+    return s, 1.0 / s
+
+
+def _invert_act(grad_out, output, act: bool, negative_slope: float):
+    """(g, z) in fp32 from the stored y: the gate and the pre-activation."""
+    g = grad_out.to(torch.float32)
+    z = output.to(torch.float32)
+    if act:
+        s, inv_s = _slope32(negative_slope)
+        pos = z > 0
+        g = torch.where(pos, g, s * g)
+        z = torch.where(pos, z, z * inv_s)
+    return g, z
+
+
+def _rscale(invstd, weight):
+    sc = invstd.to(torch.float32)
+    if weight is not None:
+        sc = sc * weight.to(torch.float32)
+    safe = torch.where(sc != 0, sc, torch.ones_like(sc))
+    return torch.where(sc != 0, 1.0 / safe, torch.zeros_like(sc))
+
+
+def batch_norm_elemt_act_(input, weight, bias, mean, invstd, act: bool,
+                          negative_slope: float = 0.0):
+    """input <- act?(input*scale + shift), written over ``input``."""
+    _check_invertible(act, negative_slope, "batch_norm_elemt_act_")
+    if input.numel() > 0:
+        input.copy_(batch_norm_elemt_act(input, None, weight, bias, mean,
+                                         invstd, act, negative_slope))
+    return input
+
+
+def batch_norm_backward_reduce_inplace(grad_out, output, invstd, weight, bias,
+                                       act: bool, input_g, weight_g, bias_g,
+                                       negative_slope: float = 0.0):
+    """The backward reductions from the stored output y:
+    sum_dy = sum g, sum_dy_xmu = sum g*((z - bias)*(1/scale)), with the fp32
+    terms the kernels form (summed in fp64)."""
+    _check_invertible(act, negative_slope,
+                      "batch_norm_backward_reduce_inplace")
+    C = output.shape[1]
+    wdtype = weight.dtype if weight is not None else output.dtype
+    g, z = _invert_act(grad_out, output, act, negative_slope)
+    rs = _rscale(invstd, weight)
+    bi = (bias.to(torch.float32) if bias is not None
+          else torch.zeros(C, dtype=torch.float32, device=output.device))
+    t = g * ((z - _chan_view(bi, output)) * _chan_view(rs, output))
+    s_dy = _flatten_to_ncs(g).to(torch.float64).sum(dim=(0, 2))
+    s_dy_xmu = _flatten_to_ncs(t).to(torch.float64).sum(dim=(0, 2))
+    combined = torch.cat([s_dy, s_dy_xmu]).to(torch.float32)
+    grad_weight = ((s_dy_xmu * invstd.to(torch.float64)).to(wdtype)
+                   if weight_g else None)
+    grad_bias = s_dy.to(wdtype) if bias_g else None
+    return combined[:C], combined[C:], grad_weight, grad_bias
+
+
+def batch_norm_backward_elemt_inplace(grad_out, output, mean, invstd, weight,
+                                      bias, sum_dy, sum_dy_xmu, count,
+                                      act: bool, negative_slope: float = 0.0):
+    """dx = a*g + (b/scale)*z + d' from the stored output y, with (a, b) of
+    the out-of-place backward and d' = -a*sum_dy/n - (b/scale)*bias."""
+    _check_invertible(act, negative_slope,
+                      "batch_norm_backward_elemt_inplace")
+    if output.numel() == 0:
+        return torch.empty_like(grad_out)
+    n = count.sum().to(torch.float32)
+    g, z = _invert_act(grad_out, output, act, negative_slope)
+    istd = invstd.to(torch.float32)
+    f1 = istd * (weight.to(torch.float32) if weight is not None else 1.0)
+    f3 = istd * istd * sum_dy_xmu.to(torch.float32) / n
+    ca = f1
+    cbz = (-f1 * f3) * _rscale(invstd, weight)
+    cdz = -(ca * (sum_dy.to(torch.float32) / n))
+    if bias is not None:
+        cdz = cdz - cbz * bias.to(torch.float32)
+    if not n > 0:
+        ca, cbz, cdz = (torch.zeros_like(istd),) * 3
+    dx = (_chan_view(ca, output) * g + _chan_view(cbz, output) * z
+          + _chan_view(cdz, output))
+    return dx.to(grad_out.dtype)
+
+
 def bn_frozen_coefs(running_mean, running_var, eps: float, weight, bias):
     """Packed fp32 [scale(C) | shift(C)] from fixed running statistics:
     scale = weight / sqrt(running_var + eps), shift = bias - running_mean*scale."""

@@ -1202,6 +1202,378 @@ __global__ void bn_bwd_fused_small_nchw(
 }
 
 // =====================================================================
+// in-place activated BN (Rota Bulo et al., 2018): the forward writes
+// y = act(scale*x + shift) OVER x, and the backward works from the stored y
+// alone.  The activation must be invertible: identity (kActNone) or
+// LeakyReLU with slope > 0 (kActLeaky), where sign(y) == sign(z):
+//   gate            g = y > 0 ? dy : slope*dy
+//   pre-activation  z = y > 0 ? y  : y*(1/slope)
+//   x - mean        = (z - bias) * (1/scale)
+// so {sum g, sum g*(x - mean)} mean what bn_bwd_reduce_partial_* emit (same
+// fp64 workspace, same finalize, same all-reduce), and with
+// x = (z - shift)/scale the usual dx = a*g + b*x + d is affine in (g, z):
+//   dx = a*g + (b/scale)*z + (d - b*shift/scale).
+// Needs scale != 0 in every channel (a zero scale gives 1/scale := 0: finite,
+// but that channel's gradients are wrong).
+// =====================================================================
+template <int ACT>
+__device__ __forceinline__ void inv_act(float yv, float& g, float& z,
+                                        float slope, float inv_slope) {
+  z = yv;
+  if (ACT == kActLeaky) {
+    const bool pos = yv > 0.f;
+    g = pos ? g : slope * g;
+    z = pos ? yv : yv * inv_slope;
+  }
+}
+
+// packed [1/scale | bias] for the reduce-from-y kernels
+template <typename WT>
+__global__ void bn_inplace_aux(const float* __restrict__ invstd,
+                               const WT* __restrict__ w,
+                               const WT* __restrict__ b, int64_t C,
+                               float* __restrict__ rscale,
+                               float* __restrict__ bias_out) {
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  const float sc = invstd[c] * (w != nullptr ? to_f(w[c]) : 1.f);
+  rscale[c] = sc != 0.f ? 1.f / sc : 0.f;
+  bias_out[c] = b != nullptr ? to_f(b[c]) : 0.f;
+}
+
+// (a, b, d) of bn_affine_bwd -> the coefficients of dx in (g, z), in place:
+//   b' = b/scale,  d' = d - b*shift/scale = -a*sum_dy/n - b'*bias
+// (the second form has no mean in it, hence no cancellation off-centre).
+template <typename WT>
+__global__ void bn_inplace_bwd_coefs(const float* __restrict__ invstd,
+                                     const WT* __restrict__ w,
+                                     const WT* __restrict__ b,
+                                     const float* __restrict__ sum_dy,
+                                     const float* __restrict__ count,
+                                     int64_t C,
+                                     const float* __restrict__ coef_a,
+                                     float* __restrict__ coef_b,
+                                     float* __restrict__ coef_d) {
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  const float n = count[0];
+  if (n <= 0.f) return;  // bn_affine_bwd wrote zeros
+  const float sc = invstd[c] * (w != nullptr ? to_f(w[c]) : 1.f);
+  const float rs = sc != 0.f ? 1.f / sc : 0.f;
+  const float bz = coef_b[c] * rs;
+  coef_b[c] = bz;
+  coef_d[c] = -(coef_a[c] * (sum_dy[c] / n)) -
+              bz * (b != nullptr ? to_f(b[c]) : 0.f);
+}
+
+// Alias-safe forward: ONE pointer, not __restrict__; every thread reads its
+// pack and writes the same pack, so no element is read after another thread
+// wrote it.  Arithmetic is bn_elemt_*'s, to the bit.
+template <typename T, int V, int ACT>
+__global__ void bn_elemt_inplace_nchw(T* xy, const float* __restrict__ scale,
+                                      const float* __restrict__ shift,
+                                      int64_t total, int64_t C, int64_t S,
+                                      float slope) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+       i * V < total; i += stride) {
+    const int64_t e = i * V;
+    const int64_t c = (e / S) % C;
+    const float sc = scale[c], sh = shift[c];
+    if (V == 1) {
+      float z = to_f(nt_load1(&xy[e])) * sc + sh;
+      z = act_fwd<ACT>(z, slope);
+      nt_store1(&xy[e], from_f<T>(z));
+    } else {
+      Pack<T, V> px = nt_load<T, V>(&xy[e]);
+      Pack<T, V> py;
+#pragma unroll
+      for (int k = 0; k < V; ++k) {
+        float z = to_f(px.v[k]) * sc + sh;
+        z = act_fwd<ACT>(z, slope);
+        py.v[k] = from_f<T>(z);
+      }
+      nt_store<T, V>(&xy[e], py);
+    }
+  }
+}
+
+template <typename T, int V, int ACT>
+__global__ void bn_elemt_inplace_nhwc(T* xy, const float* __restrict__ scale,
+                                      const float* __restrict__ shift,
+                                      int64_t total, int64_t C, float slope) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+       i * V < total; i += stride) {
+    const int64_t e = i * V;
+    const int64_t c = e % C;
+    if (V == 1) {
+      float z = to_f(nt_load1(&xy[e])) * scale[c] + shift[c];
+      z = act_fwd<ACT>(z, slope);
+      nt_store1(&xy[e], from_f<T>(z));
+    } else {
+      Pack<T, V> px = nt_load<T, V>(&xy[e]);
+      Pack<float, V> ps = *reinterpret_cast<const Pack<float, V>*>(&scale[c]);
+      Pack<float, V> pb = *reinterpret_cast<const Pack<float, V>*>(&shift[c]);
+      Pack<T, V> py;
+#pragma unroll
+      for (int k = 0; k < V; ++k) {
+        float z = to_f(px.v[k]) * ps.v[k] + pb.v[k];
+        z = act_fwd<ACT>(z, slope);
+        py.v[k] = from_f<T>(z);
+      }
+      nt_store<T, V>(&xy[e], py);
+    }
+  }
+}
+
+// backward reduce partial from y: grids, chunking, AccPair flushes and the
+// workspace layout are bn_bwd_reduce_partial_*'s.
+template <typename T, int V, int ACT>
+__global__ void bn_bwd_reduce_inplace_partial_nchw(
+    const T* __restrict__ dy, const T* __restrict__ y,
+    const float* __restrict__ rscale, const float* __restrict__ bias,
+    double* __restrict__ ws, int64_t N, int64_t C, int64_t S, int64_t chunkN,
+    int64_t chunkS, float slope, float inv_slope) {
+  const int64_t c = blockIdx.x;
+  const float rs = rscale[c], bi = bias[c];
+  const int64_t n0 = blockIdx.y * chunkN;
+  const int64_t n1 = i64min(n0 + chunkN, N);
+  const int64_t s0 = blockIdx.z * chunkS;
+  const int64_t s1 = i64min(s0 + chunkS, S);
+  AccPair acc;
+  int since_flush = 0;
+  for (int64_t n = n0; n < n1; ++n) {
+    const int64_t base = (n * C + c) * S;
+    if (V == 1) {
+      for (int64_t s = s0 + threadIdx.x; s < s1; s += blockDim.x) {
+        float g = to_f(nt_load1(&dy[base + s])), z;
+        inv_act<ACT>(to_f(nt_load1(&y[base + s])), g, z, slope, inv_slope);
+        acc.add2(g, g * ((z - bi) * rs));
+        if (++since_flush == MSBN_ACC_FLUSH) {
+          acc.flush();
+          since_flush = 0;
+        }
+      }
+    } else {
+      for (int64_t s = s0 + (int64_t)threadIdx.x * V; s < s1;
+           s += (int64_t)blockDim.x * V) {
+        Pack<T, V> pg = nt_load<T, V>(&dy[base + s]);
+        Pack<T, V> py = nt_load<T, V>(&y[base + s]);
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+          float g = to_f(pg.v[k]), z;
+          inv_act<ACT>(to_f(py.v[k]), g, z, slope, inv_slope);
+          acc.add2(g, g * ((z - bi) * rs));
+        }
+        if (++since_flush == MSBN_ACC_FLUSH / V) {
+          acc.flush();
+          since_flush = 0;
+        }
+      }
+    }
+  }
+  acc.flush();
+  double a = acc.a, b = acc.b;
+  __shared__ double lds[2 * (MSBN_BLOCK / MSBN_WAVE)];
+  block_reduce_pair(a, b, lds);
+  if (threadIdx.x == 0) {
+    const int64_t chunk = (int64_t)blockIdx.y * gridDim.z + blockIdx.z;
+    double* out = ws + (c * gridDim.y * gridDim.z + chunk) * 2;
+    out[0] = a;
+    out[1] = b;
+  }
+}
+
+template <typename T, int ACT>
+__global__ void bn_bwd_reduce_inplace_partial_nchw_flat(
+    const T* __restrict__ dy, const T* __restrict__ y,
+    const float* __restrict__ rscale, const float* __restrict__ bias,
+    double* __restrict__ ws, int64_t N, int64_t C, int64_t S,
+    int64_t chunk_len, float slope, float inv_slope) {
+  const int64_t c = blockIdx.x;
+  const float rs = rscale[c], bi = bias[c];
+  const int64_t NS = N * S;
+  const int64_t p0 = (int64_t)blockIdx.y * chunk_len;
+  const int64_t p1 = i64min(p0 + chunk_len, NS);
+  AccPair acc;
+  int since_flush = 0;
+  for (int64_t p = p0 + threadIdx.x; p < p1; p += blockDim.x) {
+    const int64_t n = p / S, s = p - n * S;
+    const int64_t e = (n * C + c) * S + s;
+    float g = to_f(nt_load1(&dy[e])), z;
+    inv_act<ACT>(to_f(nt_load1(&y[e])), g, z, slope, inv_slope);
+    acc.add2(g, g * ((z - bi) * rs));
+    if (++since_flush == MSBN_ACC_FLUSH) {
+      acc.flush();
+      since_flush = 0;
+    }
+  }
+  acc.flush();
+  double a = acc.a, b = acc.b;
+  __shared__ double lds[2 * (MSBN_BLOCK / MSBN_WAVE)];
+  block_reduce_pair(a, b, lds);
+  if (threadIdx.x == 0) {
+    double* out = ws + (c * gridDim.y + blockIdx.y) * 2;
+    out[0] = a;
+    out[1] = b;
+  }
+}
+
+template <typename T, int V, int ACT>
+__global__ void bn_bwd_reduce_inplace_partial_nhwc(
+    const T* __restrict__ dy, const T* __restrict__ y,
+    const float* __restrict__ rscale, const float* __restrict__ bias,
+    double* __restrict__ ws, int64_t rows, int64_t C, int64_t chunk_rows,
+    int lpr, float slope, float inv_slope) {
+  const int rpi = blockDim.x / lpr;
+  const int lane = threadIdx.x % lpr;
+  const int rowoff = threadIdx.x / lpr;
+  const bool active = rowoff < rpi;
+  const int64_t c = (int64_t)blockIdx.x * lpr * V + (int64_t)lane * V;
+  const bool inb = active && (c + V <= C);
+
+  AccPair acc[V];
+  if (inb) {
+    float rs[V], bi[V];
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+      rs[k] = rscale[c + k];
+      bi[k] = bias[c + k];
+    }
+    const int64_t r0 = (int64_t)blockIdx.y * chunk_rows;
+    const int64_t r1 = i64min(r0 + chunk_rows, rows);
+    int since_flush = 0;
+    for (int64_t r = r0 + rowoff; r < r1; r += rpi) {
+      Pack<T, V> pg = nt_load<T, V>(&dy[r * C + c]);
+      Pack<T, V> py = nt_load<T, V>(&y[r * C + c]);
+#pragma unroll
+      for (int k = 0; k < V; ++k) {
+        float g = to_f(pg.v[k]), z;
+        inv_act<ACT>(to_f(py.v[k]), g, z, slope, inv_slope);
+        acc[k].add2(g, g * ((z - bi[k]) * rs[k]));
+      }
+      if (++since_flush == MSBN_ACC_FLUSH) {
+#pragma unroll
+        for (int k = 0; k < V; ++k) acc[k].flush();
+        since_flush = 0;
+      }
+    }
+  }
+  double a[V], b[V];
+#pragma unroll
+  for (int k = 0; k < V; ++k) {
+    acc[k].flush();
+    a[k] = acc[k].a;
+    b[k] = acc[k].b;
+  }
+  // LDS layout and tree as in bn_bwd_reduce_partial_nhwc
+  __shared__ double sdata[MSBN_BLOCK * V * 2];
+#pragma unroll
+  for (int k = 0; k < V; ++k) {
+    sdata[k * MSBN_BLOCK + threadIdx.x] = a[k];
+    sdata[(V + k) * MSBN_BLOCK + threadIdx.x] = b[k];
+  }
+  for (int st = 1; st < rpi; st <<= 1) {
+    __syncthreads();
+    if (active && (rowoff & ((st << 1) - 1)) == 0 && rowoff + st < rpi) {
+      const int other = threadIdx.x + st * lpr;
+#pragma unroll
+      for (int k = 0; k < V; ++k) {
+        sdata[k * MSBN_BLOCK + threadIdx.x] += sdata[k * MSBN_BLOCK + other];
+        sdata[(V + k) * MSBN_BLOCK + threadIdx.x] +=
+            sdata[(V + k) * MSBN_BLOCK + other];
+      }
+    }
+  }
+  __syncthreads();
+  if (rowoff == 0 && c < C) {
+    const int64_t chunk = blockIdx.y;
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+      if (c + k < C) {
+        double* out = ws + ((c + k) * gridDim.y + chunk) * 2;
+        out[0] = sdata[k * MSBN_BLOCK + threadIdx.x];
+        out[1] = sdata[(V + k) * MSBN_BLOCK + threadIdx.x];
+      }
+    }
+  }
+}
+
+// backward elementwise from y: dx = a[c]*g + bz[c]*z + dz[c], gate and
+// pre-activation recovered from y (inv_act); cb / cd hold bz / dz
+// (bn_inplace_bwd_coefs).
+template <typename T, int V, int ACT>
+__global__ void bn_bwd_elemt_inplace_nchw(const T* __restrict__ dy,
+                                          const T* __restrict__ y,
+                                          T* __restrict__ dx,
+                                          const float* __restrict__ ca,
+                                          const float* __restrict__ cb,
+                                          const float* __restrict__ cd,
+                                          int64_t total, int64_t C, int64_t S,
+                                          float slope, float inv_slope) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+       i * V < total; i += stride) {
+    const int64_t e = i * V;
+    const int64_t c = (e / S) % C;
+    const float A = ca[c], B = cb[c], D = cd[c];
+    if (V == 1) {
+      float g = to_f(nt_load1(&dy[e])), z;
+      inv_act<ACT>(to_f(nt_load1(&y[e])), g, z, slope, inv_slope);
+      nt_store1(&dx[e], from_f<T>(A * g + B * z + D));
+    } else {
+      Pack<T, V> pg = nt_load<T, V>(&dy[e]);
+      Pack<T, V> py = nt_load<T, V>(&y[e]);
+      Pack<T, V> po;
+#pragma unroll
+      for (int k = 0; k < V; ++k) {
+        float g = to_f(pg.v[k]), z;
+        inv_act<ACT>(to_f(py.v[k]), g, z, slope, inv_slope);
+        po.v[k] = from_f<T>(A * g + B * z + D);
+      }
+      nt_store<T, V>(&dx[e], po);
+    }
+  }
+}
+
+template <typename T, int V, int ACT>
+__global__ void bn_bwd_elemt_inplace_nhwc(const T* __restrict__ dy,
+                                          const T* __restrict__ y,
+                                          T* __restrict__ dx,
+                                          const float* __restrict__ ca,
+                                          const float* __restrict__ cb,
+                                          const float* __restrict__ cd,
+                                          int64_t total, int64_t C,
+                                          float slope, float inv_slope) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+       i * V < total; i += stride) {
+    const int64_t e = i * V;
+    const int64_t c = e % C;
+    if (V == 1) {
+      float g = to_f(nt_load1(&dy[e])), z;
+      inv_act<ACT>(to_f(nt_load1(&y[e])), g, z, slope, inv_slope);
+      nt_store1(&dx[e], from_f<T>(ca[c] * g + cb[c] * z + cd[c]));
+    } else {
+      Pack<T, V> pg = nt_load<T, V>(&dy[e]);
+      Pack<T, V> py = nt_load<T, V>(&y[e]);
+      Pack<float, V> pa = *reinterpret_cast<const Pack<float, V>*>(&ca[c]);
+      Pack<float, V> pb = *reinterpret_cast<const Pack<float, V>*>(&cb[c]);
+      Pack<float, V> pd = *reinterpret_cast<const Pack<float, V>*>(&cd[c]);
+      Pack<T, V> po;
+#pragma unroll
+      for (int k = 0; k < V; ++k) {
+        float g = to_f(pg.v[k]), z;
+        inv_act<ACT>(to_f(py.v[k]), g, z, slope, inv_slope);
+        po.v[k] = from_f<T>(pa.v[k] * g + pb.v[k] * z + pd.v[k]);
+      }
+      nt_store<T, V>(&dx[e], po);
+    }
+  }
+}
+
+// =====================================================================
 // host-side helpers
 // =====================================================================
 
@@ -2161,6 +2533,277 @@ at::Tensor batch_norm_backward_elemt(
 }
 
 // ---------------------------------------------------------------------------
+// in-place activated path: forward over x, backward from y
+// ---------------------------------------------------------------------------
+namespace {
+// The in-place kernels exist for the invertible activations only.
+int inplace_act_mode(bool act, float slope, const char* name) {
+  TORCH_CHECK(!act || slope > 0.f, name,
+              ": the in-place path needs an invertible activation (identity, "
+              "or LeakyReLU with negative_slope > 0); got negative_slope=",
+              slope);
+  return act ? kActLeaky : kActNone;
+}
+
+void check_same_dense(const at::Tensor& a, const at::Tensor& ref,
+                      const char* what) {
+  TORCH_CHECK(a.sizes() == ref.sizes() && a.strides() == ref.strides() &&
+                  a.scalar_type() == ref.scalar_type() &&
+                  a.device() == ref.device(),
+              what, " must match the output's shape/strides/dtype/device");
+}
+
+at::ScalarType affine_type(const c10::optional<at::Tensor>& weight,
+                           const c10::optional<at::Tensor>& bias) {
+  const bool has_w = weight.has_value() && weight->defined();
+  const bool has_b = bias.has_value() && bias->defined();
+  TORCH_CHECK(!has_w || !has_b || weight->scalar_type() == bias->scalar_type(),
+              "weight and bias dtypes differ");
+  return has_w ? weight->scalar_type()
+               : has_b ? bias->scalar_type() : at::kFloat;
+}
+}  // namespace
+
+at::Tensor batch_norm_elemt_act_(at::Tensor& input,
+                                 const c10::optional<at::Tensor>& weight,
+                                 const c10::optional<at::Tensor>& bias,
+                                 const at::Tensor& mean,
+                                 const at::Tensor& invstd, bool act,
+                                 const c10::optional<at::Tensor>& coefs_in,
+                                 double negative_slope) {
+  const float slope = (float)negative_slope;
+  const int mode = inplace_act_mode(act, slope, "batch_norm_elemt_act_");
+  const Layout L = get_layout(input);
+  if (input.numel() == 0) return input;
+  auto stream = cur_stream();
+  auto coefs = coefs_in.has_value() && coefs_in->defined()
+                   ? *coefs_in
+                   : make_fwd_coefs(mean, invstd, weight, bias, L.C);
+  TORCH_CHECK(coefs.scalar_type() == at::kFloat && coefs.is_contiguous() &&
+                  coefs.numel() == 2 * L.C,
+              "coefs must be contiguous fp32 [2C] ([scale | shift])");
+  const float* scale = coefs.data_ptr<float>();
+  const float* shift = scale + L.C;
+  const int64_t total = input.numel();
+  MSBN_DISPATCH_FLOAT_TYPES(input.scalar_type(), "bn_elemt_inplace", [&] {
+    native_t* xy = reinterpret_cast<native_t*>(input.data_ptr<scalar_t>());
+    constexpr int VMAX = 16 / (int)sizeof(native_t);
+    const ElemtPlan plan =
+        plan_elemt(L, total, (int)sizeof(native_t), {xy}, scale);
+    MSBN_DISPATCH_V(plan.v, VMAX, [&] {
+      auto launch = [&](auto act_c) {
+        constexpr int ACT_ = decltype(act_c)::value;
+        if (!L.nhwc) {
+          hipLaunchKernelGGL((bn_elemt_inplace_nchw<native_t, VV, ACT_>),
+                             dim3(plan.grid), dim3(MSBN_BLOCK), 0, stream, xy,
+                             scale, shift, total, L.C, L.S, slope);
+        } else {
+          hipLaunchKernelGGL((bn_elemt_inplace_nhwc<native_t, VV, ACT_>),
+                             dim3(plan.grid), dim3(MSBN_BLOCK), 0, stream, xy,
+                             scale, shift, total, L.C, slope);
+        }
+      };
+      if (mode == kActLeaky) launch(ActC<kActLeaky>{});
+      else launch(ActC<kActNone>{});
+    });
+  });
+  return input;
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor>
+batch_norm_backward_reduce_inplace(
+    const at::Tensor& grad_out, const at::Tensor& output,
+    const at::Tensor& invstd, const c10::optional<at::Tensor>& weight,
+    const c10::optional<at::Tensor>& bias, bool act, bool input_g,
+    bool weight_g, bool bias_g, const c10::optional<at::Tensor>& coefs_in,
+    double negative_slope) {
+  (void)input_g;
+  (void)coefs_in;  // 1/scale is formed from invstd*weight, as the coefs were
+  const float slope = (float)negative_slope;
+  const int mode =
+      inplace_act_mode(act, slope, "batch_norm_backward_reduce_inplace");
+  const float inv_slope = act ? 1.f / slope : 1.f;
+  const Layout L = get_layout(output);
+  const auto wtype = affine_type(weight, bias);
+  auto f32 = output.options().dtype(at::kFloat);
+  const auto gtype = weight.has_value() && weight->defined()
+                         ? weight->scalar_type()
+                         : output.scalar_type();
+  auto wopts = output.options().dtype(gtype);
+  if (output.numel() == 0) {
+    auto combined0 = at::zeros({2 * L.C}, f32);
+    at::Tensor gw0, gb0;
+    if (weight_g) gw0 = at::zeros({L.C}, wopts);
+    if (bias_g) gb0 = at::zeros({L.C}, wopts);
+    return {combined0.narrow(0, 0, L.C), combined0.narrow(0, L.C, L.C), gw0,
+            gb0};
+  }
+  check_same_dense(grad_out, output, "grad_out");
+  // ONE contiguous buffer for [sum_dy | sum_dy_xmu] -> single all_reduce.
+  auto combined = at::empty({2 * L.C}, f32);
+  auto sum_dy = combined.narrow(0, 0, L.C);
+  auto sum_dy_xmu = combined.narrow(0, L.C, L.C);
+  at::Tensor grad_weight, grad_bias;
+  if (weight_g) grad_weight = at::empty({L.C}, wopts);
+  if (bias_g) grad_bias = at::empty({L.C}, wopts);
+
+  auto stream = cur_stream();
+  auto aux = at::empty({2 * L.C}, f32);
+  float* rscale = aux.data_ptr<float>();
+  float* bias_f = rscale + L.C;
+  const int cgrid = (int)cdiv(L.C, MSBN_BLOCK);
+  MSBN_DISPATCH_RSTAT(wtype, "bn_inplace_aux", [&] {
+    const rstat_t* w =
+        weight.has_value() && weight->defined()
+            ? reinterpret_cast<const rstat_t*>(weight->data_ptr())
+            : nullptr;
+    const rstat_t* b = bias.has_value() && bias->defined()
+                           ? reinterpret_cast<const rstat_t*>(bias->data_ptr())
+                           : nullptr;
+    hipLaunchKernelGGL((bn_inplace_aux<rstat_t>), dim3(cgrid),
+                       dim3(MSBN_BLOCK), 0, stream, invstd.data_ptr<float>(),
+                       w, b, L.C, rscale, bias_f);
+  });
+
+  MSBN_DISPATCH_FLOAT_TYPES(output.scalar_type(), "bn_bwd_reduce_inplace", [&] {
+    const native_t* y =
+        reinterpret_cast<const native_t*>(output.data_ptr<scalar_t>());
+    const native_t* dy =
+        reinterpret_cast<const native_t*>(grad_out.data_ptr<scalar_t>());
+    constexpr int VMAX = 16 / (int)sizeof(native_t);
+    const ReducePlan plan = plan_reduce(L, (int)sizeof(native_t), {y, dy});
+    const int nchunks = plan.nchunks;
+    at::Tensor ws = at::empty({(int64_t)nchunks * L.C * 2},
+                              output.options().dtype(at::kDouble));
+    auto launch = [&](auto act_c) {
+      constexpr int ACT_ = decltype(act_c)::value;
+      if (plan.path == RedPath::NchwFlat) {
+        const auto& g = plan.flat;
+        hipLaunchKernelGGL(
+            (bn_bwd_reduce_inplace_partial_nchw_flat<native_t, ACT_>), g.grid,
+            dim3(MSBN_BLOCK), 0, stream, dy, y, rscale, bias_f,
+            ws.data_ptr<double>(), L.N, L.C, L.S, g.chunk_len, slope,
+            inv_slope);
+      } else if (plan.path == RedPath::NchwVec) {
+        const auto& g = plan.nchw;
+        MSBN_DISPATCH_V(plan.v, VMAX, [&] {
+          hipLaunchKernelGGL(
+              (bn_bwd_reduce_inplace_partial_nchw<native_t, VV, ACT_>),
+              g.grid, dim3(MSBN_BLOCK), 0, stream, dy, y, rscale, bias_f,
+              ws.data_ptr<double>(), L.N, L.C, L.S, g.chunkN, g.chunkS, slope,
+              inv_slope);
+        });
+      } else {
+        const auto& g = plan.nhwc;
+        MSBN_DISPATCH_V(plan.v, VMAX, [&] {
+          hipLaunchKernelGGL(
+              (bn_bwd_reduce_inplace_partial_nhwc<native_t, VV, ACT_>),
+              g.grid, dim3(MSBN_BLOCK), 0, stream, dy, y, rscale, bias_f,
+              ws.data_ptr<double>(), L.rows, L.C, g.chunk_rows, g.lpr, slope,
+              inv_slope);
+        });
+      }
+    };
+    if (mode == kActLeaky) launch(ActC<kActLeaky>{});
+    else launch(ActC<kActNone>{});
+    const int fgrid = (int)cdiv(L.C, kFinalizeWavesPerBlock);
+    MSBN_DISPATCH_RSTAT(gtype, "bn_bwd_reduce_inplace", [&] {
+      rstat_t* gw = weight_g ? reinterpret_cast<rstat_t*>(grad_weight.data_ptr())
+                             : nullptr;
+      rstat_t* gb =
+          bias_g ? reinterpret_cast<rstat_t*>(grad_bias.data_ptr()) : nullptr;
+      hipLaunchKernelGGL((bn_bwd_reduce_finalize<rstat_t>), dim3(fgrid),
+                         dim3(MSBN_BLOCK), 0, stream, ws.data_ptr<double>(),
+                         nchunks, L.C, invstd.data_ptr<float>(),
+                         sum_dy.data_ptr<float>(),
+                         sum_dy_xmu.data_ptr<float>(), gw, gb);
+    });
+  });
+  return {sum_dy, sum_dy_xmu, grad_weight, grad_bias};
+}
+
+at::Tensor batch_norm_backward_elemt_inplace(
+    const at::Tensor& grad_out, const at::Tensor& output,
+    const at::Tensor& mean, const at::Tensor& invstd,
+    const c10::optional<at::Tensor>& weight,
+    const c10::optional<at::Tensor>& bias, const at::Tensor& sum_dy,
+    const at::Tensor& sum_dy_xmu, const at::Tensor& count, bool act,
+    const c10::optional<at::Tensor>& coefs_in, double negative_slope) {
+  (void)coefs_in;
+  const float slope = (float)negative_slope;
+  const int mode =
+      inplace_act_mode(act, slope, "batch_norm_backward_elemt_inplace");
+  const float inv_slope = act ? 1.f / slope : 1.f;
+  const Layout L = get_layout(output);
+  auto dx = at::empty_like(grad_out);
+  if (output.numel() == 0) return dx;
+  check_same_dense(grad_out, output, "grad_out");
+  // total count as a device fp32 scalar (no host sync)
+  at::Tensor count_sum;
+  if (count.numel() == 1 && count.scalar_type() == at::kFloat) {
+    count_sum = count;
+  } else {
+    count_sum = count.to(at::kFloat).sum().reshape({1});
+  }
+  auto stream = cur_stream();
+  auto coefs = at::empty({3 * L.C}, output.options().dtype(at::kFloat));
+  float* ca = coefs.data_ptr<float>();
+  float* cb = ca + L.C;
+  float* cd = cb + L.C;
+  const int cgrid = (int)cdiv(L.C, MSBN_BLOCK);
+  MSBN_DISPATCH_RSTAT(affine_type(weight, bias), "bn_bwd_elemt_inplace", [&] {
+    const rstat_t* w =
+        weight.has_value() && weight->defined()
+            ? reinterpret_cast<const rstat_t*>(weight->data_ptr())
+            : nullptr;
+    const rstat_t* b = bias.has_value() && bias->defined()
+                           ? reinterpret_cast<const rstat_t*>(bias->data_ptr())
+                           : nullptr;
+    hipLaunchKernelGGL((bn_affine_bwd<rstat_t>), dim3(cgrid), dim3(MSBN_BLOCK),
+                       0, stream, mean.data_ptr<float>(),
+                       invstd.data_ptr<float>(), w, sum_dy.data_ptr<float>(),
+                       sum_dy_xmu.data_ptr<float>(),
+                       count_sum.data_ptr<float>(), L.C, ca, cb, cd);
+    hipLaunchKernelGGL((bn_inplace_bwd_coefs<rstat_t>), dim3(cgrid),
+                       dim3(MSBN_BLOCK), 0, stream, invstd.data_ptr<float>(),
+                       w, b, sum_dy.data_ptr<float>(),
+                       count_sum.data_ptr<float>(), L.C, ca, cb, cd);
+  });
+
+  const int64_t total = output.numel();
+  MSBN_DISPATCH_FLOAT_TYPES(output.scalar_type(), "bn_bwd_elemt_inplace", [&] {
+    const native_t* y =
+        reinterpret_cast<const native_t*>(output.data_ptr<scalar_t>());
+    const native_t* dy =
+        reinterpret_cast<const native_t*>(grad_out.data_ptr<scalar_t>());
+    native_t* o = reinterpret_cast<native_t*>(dx.data_ptr<scalar_t>());
+    constexpr int VMAX = 16 / (int)sizeof(native_t);
+    // ca / cb / cd are this op's own aligned buffer: C % V == 0 (pick_v)
+    // keeps every V-float pack of them aligned
+    const ElemtPlan plan =
+        plan_elemt(L, total, (int)sizeof(native_t), {y, dy, o}, nullptr);
+    MSBN_DISPATCH_V(plan.v, VMAX, [&] {
+      auto launch = [&](auto act_c) {
+        constexpr int ACT_ = decltype(act_c)::value;
+        if (!L.nhwc) {
+          hipLaunchKernelGGL((bn_bwd_elemt_inplace_nchw<native_t, VV, ACT_>),
+                             dim3(plan.grid), dim3(MSBN_BLOCK), 0, stream, dy,
+                             y, o, ca, cb, cd, total, L.C, L.S, slope,
+                             inv_slope);
+        } else {
+          hipLaunchKernelGGL((bn_bwd_elemt_inplace_nhwc<native_t, VV, ACT_>),
+                             dim3(plan.grid), dim3(MSBN_BLOCK), 0, stream, dy,
+                             y, o, ca, cb, cd, total, L.C, slope, inv_slope);
+        }
+      };
+      if (mode == kActLeaky) launch(ActC<kActLeaky>{});
+      else launch(ActC<kActNone>{});
+    });
+  });
+  return dx;
+}
+
+// ---------------------------------------------------------------------------
 // frozen path (running-stat normalization with autograd on)
 // ---------------------------------------------------------------------------
 at::Tensor bn_frozen_coefs(const at::Tensor& running_mean,
@@ -2533,7 +3176,8 @@ std::tuple<std::string, std::map<std::string, int64_t>> launch_plan(
   }
 
   const Layout L = get_layout(input);
-  if (kind == "stats" || kind == "bwd_reduce") {
+  if (kind == "stats" || kind == "bwd_reduce" ||
+      kind == "bwd_reduce_inplace") {
     const ReducePlan p = plan_reduce(L, esize, ptrs);
     path = p.path == RedPath::Nhwc       ? "nhwc"
            : p.path == RedPath::NchwFlat ? "nchw_flat"
@@ -2557,7 +3201,8 @@ std::tuple<std::string, std::map<std::string, int64_t>> launch_plan(
     return {path, d};
   }
   TORCH_CHECK(kind == "elemt" || kind == "bwd_elemt" ||
-                  kind == "frozen_bwd_elemt",
+                  kind == "frozen_bwd_elemt" || kind == "elemt_inplace" ||
+                  kind == "bwd_elemt_inplace",
               "launch_plan: unknown kind '", kind, "'");
   const ElemtPlan p = plan_elemt(L, input.numel(), esize, ptrs, coef);
   path = L.nhwc ? "nhwc" : (p.v == 1 ? "nchw_flat" : "nchw_vec");

@@ -175,6 +175,39 @@ std::tuple<at::Tensor, at::Tensor> batch_norm_backward_elemt_act(
     bool want_res_grad, const c10::optional<at::Tensor>& coefs_in,
     double negative_slope);
 
+// ---- in-place activated path (forward over x, backward from y) ------------
+// The forward writes y = act(x*scale + shift) over `input` and returns it;
+// the backward ops take that stored y instead of x and invert the activation
+// (identity, or LeakyReLU with negative_slope > 0: `act` with any other slope
+// is an error) and the affine map:  z = y > 0 ? y : y/slope,
+// x - mean = (z - bias)/scale.  Needs weight*invstd != 0 in every channel; a
+// zero gives finite but wrong gradients for that channel.  Two-stage kernels
+// only (no small-plane variant).  sum_dy / sum_dy_xmu / grad_weight /
+// grad_bias mean what batch_norm_backward_reduce_act returns.
+at::Tensor batch_norm_elemt_act_(at::Tensor& input,
+                                 const c10::optional<at::Tensor>& weight,
+                                 const c10::optional<at::Tensor>& bias,
+                                 const at::Tensor& mean,
+                                 const at::Tensor& invstd, bool act,
+                                 const c10::optional<at::Tensor>& coefs_in,
+                                 double negative_slope);
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor>
+batch_norm_backward_reduce_inplace(
+    const at::Tensor& grad_out, const at::Tensor& output,
+    const at::Tensor& invstd, const c10::optional<at::Tensor>& weight,
+    const c10::optional<at::Tensor>& bias, bool act, bool input_g,
+    bool weight_g, bool bias_g, const c10::optional<at::Tensor>& coefs_in,
+    double negative_slope);
+
+at::Tensor batch_norm_backward_elemt_inplace(
+    const at::Tensor& grad_out, const at::Tensor& output,
+    const at::Tensor& mean, const at::Tensor& invstd,
+    const c10::optional<at::Tensor>& weight,
+    const c10::optional<at::Tensor>& bias, const at::Tensor& sum_dy,
+    const at::Tensor& sum_dy_xmu, const at::Tensor& count, bool act,
+    const c10::optional<at::Tensor>& coefs_in, double negative_slope);
+
 // ---- launch plan (host only, launches nothing) ----------------------------
 // Which kernel path a call would take and how far its loops run, decided by
 // the same host code the ops launch with.  kind / tensors:
@@ -185,6 +218,9 @@ std::tuple<at::Tensor, at::Tensor> batch_norm_backward_elemt_act(
 //   "bwd_elemt"        input = x,        others = {grad_out, residual}, coefs
 //   "frozen_bwd_elemt" input = grad_out, others = {x, residual}, coefs
 //   "fused_local"      input = x,        others = {residual}
+//   "elemt_inplace"      input = x,      coefs
+//   "bwd_reduce_inplace" input = y,      others = {grad_out}
+//   "bwd_elemt_inplace"  input = y,      others = {grad_out}
 // (pass only what the op itself would dereference).  Returns (path, numbers):
 // path is "nchw_vec" | "nchw_flat" | "nhwc" | "small_plane" | "ineligible";
 // numbers always hold V and trips (most loop iterations of one thread);

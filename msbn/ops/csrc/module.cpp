@@ -63,6 +63,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("relu_mask"), py::arg("want_res_grad"),
         py::arg("coefs") = py::none(), py::arg("negative_slope") = 0.0);
 
+  m.def("batch_norm_elemt_act_", &msbn::batch_norm_elemt_act_,
+        py::arg("input"), py::arg("weight"), py::arg("bias"), py::arg("mean"),
+        py::arg("invstd"), py::arg("act"), py::arg("coefs") = py::none(),
+        py::arg("negative_slope") = 0.0);
+  m.def("batch_norm_backward_reduce_inplace",
+        &msbn::batch_norm_backward_reduce_inplace, py::arg("grad_out"),
+        py::arg("output"), py::arg("invstd"), py::arg("weight"),
+        py::arg("bias"), py::arg("act"), py::arg("input_g"),
+        py::arg("weight_g"), py::arg("bias_g"), py::arg("coefs") = py::none(),
+        py::arg("negative_slope") = 0.0);
+  m.def("batch_norm_backward_elemt_inplace",
+        &msbn::batch_norm_backward_elemt_inplace, py::arg("grad_out"),
+        py::arg("output"), py::arg("mean"), py::arg("invstd"),
+        py::arg("weight"), py::arg("bias"), py::arg("sum_dy"),
+        py::arg("sum_dy_xmu"), py::arg("count"), py::arg("act"),
+        py::arg("coefs") = py::none(), py::arg("negative_slope") = 0.0);
+
   m.def("bn_frozen_coefs", &msbn::bn_frozen_coefs, py::arg("running_mean"),
         py::arg("running_var"), py::arg("eps"), py::arg("weight"),
         py::arg("bias"));
