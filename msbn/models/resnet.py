@@ -16,7 +16,7 @@ import torch
 import torch.nn as nn
 
 from msbn.nn import BatchNorm2d, SyncBatchNorm
-from msbn.nn.fused import SyncBatchNormAct2d
+from msbn.nn.fused import SyncBatchNormAct2d, bn_act_maxpool
 
 
 def conv3x3(cin, cout, stride=1):
@@ -139,6 +139,8 @@ class ResNet(nn.Module):
         # it over as a (main, skip) pair (_last_bn).  Same math either way;
         # False keeps autograd's own gradient add at each fork.
         self.fork_grads = fork_grads and fused
+        # fused models: bn1 + relu + maxpool run as one layer (_stem)
+        self.stem_pool = fused
         self.inplanes = 64
         self.conv1 = nn.Conv2d(in_chans, 64, 7, stride=2, padding=3, bias=False)
         if fused:
@@ -180,6 +182,16 @@ class ResNet(nn.Module):
     def _stem(self, x):
         x = self.conv1(x)
         if self.fused:
+            # bn1 + relu + maxpool as one layer where eligible (training-mode
+            # SyncBatchNormAct2d, MaxPool2d(3, 2, 1), channels-last on the
+            # GPU), else exactly maxpool(bn1(x)).  With fork_grads the result
+            # goes to layer1[0] as a (main, skip) pair, so its conv1 and skip
+            # gradients reach the stem's backward kernels unsummed.
+            # stem_pool = False keeps the composition (same results).
+            if (getattr(self, "stem_pool", True)
+                    and isinstance(self.bn1, SyncBatchNormAct2d)):
+                return bn_act_maxpool(self.bn1, self.maxpool, x,
+                                      fork=getattr(self, "fork_grads", False))
             return self.maxpool(self.bn1(x))
         return self.maxpool(self.relu(self.bn1(x)))
 

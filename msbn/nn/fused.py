@@ -268,6 +268,178 @@ class SyncBatchNormActFunction(torch.autograd.Function):
         )
 
 
+class SyncBatchNormActPoolFunction(torch.autograd.Function):
+    """``max_pool2d(act(bn(x)), 3, 2, 1)`` as one layer (the ResNet stem).
+
+    The forward reads x once and writes the pooled output and one byte per
+    pooled element (the window code); the full-size activation and the pool's
+    int64 indices never exist.  The backward kernels gather each x element's
+    gradient from the pooled gradient(s) through the codes, so neither the
+    full-size pooled gradient nor (with ``fork``) the eager sum of the two
+    consumers' gradients is materialised.  Saved for backward: x, the codes
+    and per-channel vectors.  Statistics, their sync and the running update
+    are those of SyncBatchNormActFunction; always the two-stage kernels.
+    Results are bit-identical to the composition.  Callers check
+    eligibility (``stem_pool_eligible``)."""
+
+    @staticmethod
+    def forward(
+        ctx,
+        input: torch.Tensor,
+        weight: Optional[torch.Tensor],
+        bias: Optional[torch.Tensor],
+        running_mean: Optional[torch.Tensor],
+        running_var: Optional[torch.Tensor],
+        eps: float,
+        momentum: float,
+        process_group,
+        world_size: int,
+        relu: bool,
+        negative_slope: float = 0.0,
+        fork: bool = False,
+    ):
+        if weight is not None:
+            weight = weight.contiguous()
+        if bias is not None:
+            bias = bias.contiguous()
+        use_sync = world_size > 1 or (
+            process_group is not None and _force_sync()
+        )
+        mean, invstd, count_sum, coefs = compute_sync_stats(
+            input, eps, momentum, running_mean, running_var,
+            process_group, world_size, weight, bias, want_coefs=True,
+        )
+        pooled, codes = ops.batch_norm_elemt_act_pool(
+            input, weight, bias, mean, invstd, relu, coefs, negative_slope
+        )
+        ctx.has_coefs = coefs is not None
+        saved = (input, codes, weight, bias, mean, invstd, count_sum)
+        ctx.save_for_backward(*(saved + ((coefs,) if ctx.has_coefs else ())))
+        ctx.relu = relu
+        ctx.negative_slope = negative_slope
+        ctx.process_group = process_group
+        ctx.use_sync = use_sync
+        if not fork:
+            return pooled
+        # an unused output then arrives as None, not as a zero fill
+        ctx.set_materialize_grads(False)
+        return pooled, pooled.detach()
+
+    @staticmethod
+    def backward(ctx, grad_output, grad_skip=None):
+        if grad_output is None:  # fork with only the second output used
+            grad_output, grad_skip = grad_skip, None
+        if grad_output is None:
+            return (None,) * 12
+        saved = ctx.saved_tensors
+        input, codes, weight, bias, mean, invstd, count_sum = saved[:7]
+        coefs = saved[7] if ctx.has_coefs else None
+        grad_output = _match_layout(grad_output, codes)
+        if grad_skip is not None:
+            grad_skip = _match_layout(grad_skip, codes)
+        relu, slope = ctx.relu, ctx.negative_slope
+        process_group = ctx.process_group
+        need_input_g = ctx.needs_input_grad[0]
+        need_weight_g = weight is not None and ctx.needs_input_grad[1]
+        need_bias_g = bias is not None and ctx.needs_input_grad[2]
+        C = int(input.shape[1])
+
+        sum_dy, sum_dy_xmu, grad_weight, grad_bias = (
+            ops.batch_norm_backward_reduce_act_pool(
+                grad_output, grad_skip, codes, input, mean, invstd, weight,
+                bias, relu, need_input_g, need_weight_g, need_bias_g, coefs,
+                slope,
+            )
+        )
+        grad_input = None
+        if need_input_g:
+            if ctx.use_sync:
+                combined, copied = _combined_view(sum_dy, sum_dy_xmu, C)
+                from msbn.utils import debug as _dbg
+                if _dbg.enabled():
+                    _dbg.verify_collective("syncbn.bwd.all_reduce",
+                                           combined, process_group)
+                dist.all_reduce(combined, dist.ReduceOp.SUM,
+                                group=process_group)
+                from msbn.utils.logging import comm_log
+                comm_log.record("all_reduce", combined.numel() * 4,
+                                f"syncbn bwd C={C}")
+                if copied:
+                    sum_dy, sum_dy_xmu = combined[:C], combined[C:]
+            grad_input = ops.batch_norm_backward_elemt_act_pool(
+                grad_output, grad_skip, codes, input, mean, invstd, weight,
+                bias, sum_dy, sum_dy_xmu, count_sum, relu, coefs, slope,
+            )
+        return (
+            grad_input,
+            grad_weight if need_weight_g else None,
+            grad_bias if need_bias_g else None,
+            None, None, None, None, None, None, None, None, None,
+        )
+
+
+def stem_pool_eligible(bn, pool, input: torch.Tensor) -> bool:
+    """True when ``pool(bn(input))`` can run as SyncBatchNormActPoolFunction:
+    a training-mode out-of-place SyncBatchNormAct2d, MaxPool2d(3, 2, 1)
+    (dilation 1, floor mode, no indices) and a non-empty dense channels-last
+    CUDA input.  Everything else runs the composition, modules with hooks
+    included (the fused route does not go through their ``__call__``)."""
+    def _pair(v):
+        return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+
+    def _hooked(m):
+        return bool(m._forward_hooks or m._forward_pre_hooks
+                    or m._backward_hooks or m._backward_pre_hooks)
+
+    return (
+        type(bn) is SyncBatchNormAct2d
+        and not getattr(bn, "inplace", False)
+        and not _hooked(bn) and not _hooked(pool)
+        and (bn.training
+             or (bn.running_mean is None and bn.running_var is None))
+        and type(pool) is torch.nn.MaxPool2d
+        and _pair(pool.kernel_size) == (3, 3)
+        and _pair(pool.stride) == (2, 2)
+        and _pair(pool.padding) == (1, 1)
+        and _pair(pool.dilation) == (1, 1)
+        and not pool.ceil_mode and not pool.return_indices
+        and input.is_cuda and input.dim() == 4 and input.numel() > 0
+        and input.is_contiguous(memory_format=torch.channels_last)
+        and input.dtype in (torch.float32, torch.bfloat16, torch.float16)
+    )
+
+
+def bn_act_maxpool(bn, pool, input: torch.Tensor, fork: bool = False):
+    """``pool(bn(input))`` for a SyncBatchNormAct2d ``bn`` and a MaxPool2d
+    ``pool``, fused into SyncBatchNormActPoolFunction where eligible and the
+    plain composition otherwise.  ``fork=True`` returns a ``(main, skip)``
+    pair for a result with two consumers (see SyncBatchNormAct2d.forward);
+    the composition's pair is the same tensor twice."""
+    if not stem_pool_eligible(bn, pool, input):
+        y = pool(bn(input))
+        return (y, y) if fork else y
+    bn._check_input_dim(input)
+    bn._check_non_zero_input_channels(input)
+    if bn.training and bn.track_running_stats:
+        if bn.num_batches_tracked is not None:
+            bn.num_batches_tracked.add_(1)
+    factor = _momentum_factor(bn) if bn.training else (
+        bn.momentum if bn.momentum is not None else 0.0
+    )
+    process_group = None
+    world_size = 1
+    if dist.is_available() and dist.is_initialized():
+        process_group = bn.process_group or dist.group.WORLD
+        world_size = dist.get_world_size(process_group)
+    running_mean = bn.running_mean if bn.track_running_stats else None
+    running_var = bn.running_var if bn.track_running_stats else None
+    return SyncBatchNormActPoolFunction.apply(
+        input, bn.weight, bn.bias, running_mean, running_var, bn.eps, factor,
+        process_group, world_size, bn.relu,
+        getattr(bn, "negative_slope", 0.0), fork,
+    )
+
+
 class InPlaceSyncBatchNormActFunction(torch.autograd.Function):
     """In-Place Activated SyncBatchNorm (Rota Bulo et al., 2018): the output
     ``y = act(bn(x))`` is written over ``x`` and the backward works from ``y``

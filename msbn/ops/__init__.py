@@ -265,6 +265,60 @@ def batch_norm_backward_elemt_act(grad_out, input, residual, mean, invstd,
     )
 
 
+def batch_norm_elemt_act_pool(input, weight, bias, mean, invstd, relu: bool,
+                              coefs=None, negative_slope: float = 0.0):
+    """``max_pool2d(act(x*scale + shift), 3, 2, 1)`` without the activation
+    tensor: returns ``(pooled, codes)``.  The maximum is taken over the values
+    rounded to the input dtype (first maximum in kh, kw order; NaN wins, as
+    in torch), and ``codes`` holds one uint8 ``kh*3 + kw`` per pooled
+    element.  4-D channels-last input on the GPU."""
+    if input.is_cuda:
+        return _require_hip().batch_norm_elemt_act_pool(
+            input, weight, bias, mean, invstd, relu, coefs, negative_slope
+        )
+    return _ref.batch_norm_elemt_act_pool(
+        input, weight, bias, mean, invstd, relu, negative_slope
+    )
+
+
+def batch_norm_backward_reduce_act_pool(grad_out, grad_out2, codes, input,
+                                        mean, invstd, weight, bias, relu_mask,
+                                        input_g, weight_g, bias_g, coefs=None,
+                                        negative_slope: float = 0.0):
+    """``batch_norm_backward_reduce_act`` for a layer run through
+    ``batch_norm_elemt_act_pool``: ``grad_out`` (and ``grad_out2``, the second
+    gradient of a forked output, or None) are POOLED gradients; the gradient
+    of each x element is gathered through ``codes`` inside the kernel, with
+    the roundings of the eager add and of the pool's own backward."""
+    if input.is_cuda:
+        return _require_hip().batch_norm_backward_reduce_act_pool(
+            grad_out, grad_out2, codes, input, mean, invstd, weight, bias,
+            relu_mask, input_g, weight_g, bias_g, coefs, negative_slope,
+        )
+    return _ref.batch_norm_backward_reduce_act_pool(
+        grad_out, grad_out2, codes, input, mean, invstd, weight, bias,
+        relu_mask, input_g, weight_g, bias_g, negative_slope,
+    )
+
+
+def batch_norm_backward_elemt_act_pool(grad_out, grad_out2, codes, input,
+                                       mean, invstd, weight, bias, sum_dy,
+                                       sum_dy_xmu, count, relu_mask,
+                                       coefs=None,
+                                       negative_slope: float = 0.0):
+    """Second backward pass of the pooled layer: gathers the same gradient
+    again and returns ``dx`` (full size)."""
+    if input.is_cuda:
+        return _require_hip().batch_norm_backward_elemt_act_pool(
+            grad_out, grad_out2, codes, input, mean, invstd, weight, bias,
+            sum_dy, sum_dy_xmu, count, relu_mask, coefs, negative_slope,
+        )
+    return _ref.batch_norm_backward_elemt_act_pool(
+        grad_out, grad_out2, codes, input, mean, invstd, weight, bias,
+        sum_dy, sum_dy_xmu, count, relu_mask, negative_slope,
+    )
+
+
 def batch_norm_elemt_act_(input, weight, bias, mean, invstd, act: bool,
                           coefs=None, negative_slope: float = 0.0):
     """In place: ``input <- act(input*scale + shift)``; returns ``input``.
@@ -371,6 +425,10 @@ def launch_plan(kind: str, input: torch.Tensor, others=(), coefs=None) -> dict:
       ``"elemt_inplace"``       input = x, coefs
       ``"bwd_reduce_inplace"``  input = y, others = (grad_out,)
       ``"bwd_elemt_inplace"``   input = y, others = (grad_out,)
+      ``"elemt_pool"``        input = x, others = (pooled, codes), coefs
+      ``"bwd_reduce_pool"``   input = x, others = (grad_out, grad_out2, codes)
+      ``"bwd_elemt_pool"``    input = x, others = (grad_out, grad_out2,
+                                                   codes), coefs
     ``None`` entries of ``others`` are absent tensors.
 
     Returns a dict with ``path`` (``"nchw_vec"``, ``"nchw_flat"``, ``"nhwc"``,
@@ -391,6 +449,9 @@ __all__ = [
     "launch_plan",
     "bn_frozen_coefs",
     "batch_norm_frozen_backward_elemt",
+    "batch_norm_elemt_act_pool",
+    "batch_norm_backward_reduce_act_pool",
+    "batch_norm_backward_elemt_act_pool",
     "batch_norm_elemt_act_",
     "batch_norm_backward_reduce_inplace",
     "batch_norm_backward_elemt_inplace",

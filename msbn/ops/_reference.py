@@ -211,6 +211,120 @@ def batch_norm_backward_elemt_act(
     return dx, dres
 
 
+# ---- stem pool fusion: bn + act + MaxPool2d(3, 2, 1) -----------------------
+# Same code convention and rounding points as the kernels: the maximum is
+# taken over y ROUNDED to the input dtype, scanning kh then kw ascending with
+# `val > max or isnan(val)` (first maximum wins); the code of a pooled
+# element is kh*3 + kw.  The backward gathers, per x element, the pooled
+# gradient of every window whose code names it: fp32 sum in ascending
+# (oh, ow) order, rounded to the input dtype once.
+
+def pool_out_size(size: int) -> int:
+    """Output length of the fixed kernel-3 / stride-2 / padding-1 pool."""
+    return (size - 1) // 2 + 1
+
+
+def _pooled_like(t: torch.Tensor, ref: torch.Tensor) -> torch.Tensor:
+    if ref.is_contiguous(memory_format=torch.channels_last):
+        return t.contiguous(memory_format=torch.channels_last)
+    return t.contiguous()
+
+
+def batch_norm_elemt_act_pool(input, weight, bias, mean, invstd, relu: bool,
+                              negative_slope: float = 0.0):
+    """(pooled, codes) of maxpool_3_2_1(act?(x*scale + shift)); codes uint8."""
+    y = batch_norm_elemt_act(input, None, weight, bias, mean, invstd, relu,
+                             negative_slope)
+    N, C, H, W = y.shape
+    OH, OW = pool_out_size(H), pool_out_size(W)
+    yp = torch.nn.functional.pad(y.to(torch.float32), (1, 1, 1, 1),
+                                 value=float("-inf"))
+    best = torch.full((N, C, OH, OW), float("-inf"), dtype=torch.float32,
+                      device=y.device)
+    # first window position inside the image (what an all -inf window keeps)
+    first_h = torch.zeros(OH, dtype=torch.uint8, device=y.device)
+    first_w = torch.zeros(OW, dtype=torch.uint8, device=y.device)
+    first_h[0] = 3
+    first_w[0] = 1
+    codes = (first_h.reshape(1, 1, OH, 1) + first_w.reshape(1, 1, 1, OW)
+             ).expand(N, C, OH, OW).clone()
+    for kh in range(3):
+        for kw in range(3):
+            val = yp[:, :, kh:kh + 2 * OH - 1:2, kw:kw + 2 * OW - 1:2]
+            upd = (val > best) | torch.isnan(val)
+            best = torch.where(upd, val, best)
+            codes = torch.where(upd, torch.full_like(codes, kh * 3 + kw),
+                                codes)
+    return (_pooled_like(best.to(input.dtype), input),
+            _pooled_like(codes, input))
+
+
+def pool_codes_to_indices(codes: torch.Tensor, H: int, W: int) -> torch.Tensor:
+    """torch's max_pool2d indices (h*W + w of the chosen element, int64)."""
+    OH, OW = codes.shape[2], codes.shape[3]
+    c = codes.to(torch.int64)
+    oh = torch.arange(OH, device=codes.device).reshape(1, 1, OH, 1)
+    ow = torch.arange(OW, device=codes.device).reshape(1, 1, 1, OW)
+    return (2 * oh - 1 + c // 3) * W + (2 * ow - 1 + c % 3)
+
+
+def pool_gather_grad(grad_out, grad_out2, codes, input):
+    """The full-size gradient the pool's backward stores, in the input
+    dtype: zero where no window chose the element."""
+    g = grad_out
+    if grad_out2 is not None:
+        g = grad_out + grad_out2  # one rounding, as the eager add
+    g = g.to(torch.float32)
+    N, C, H, W = input.shape
+    OH, OW = codes.shape[2], codes.shape[3]
+    full = torch.zeros((N, C, H, W), dtype=torch.float32,
+                       device=input.device)
+    # ascending (oh, ow) for a fixed element == descending (kh, kw)
+    for kh in (2, 1, 0):
+        lo_h = 1 if kh == 0 else 0
+        hi_h = min(OH - 1, (H - kh) // 2)
+        for kw in (2, 1, 0):
+            lo_w = 1 if kw == 0 else 0
+            hi_w = min(OW - 1, (W - kw) // 2)
+            if hi_h < lo_h or hi_w < lo_w:
+                continue
+            sel = (slice(None), slice(None), slice(lo_h, hi_h + 1),
+                   slice(lo_w, hi_w + 1))
+            part = torch.where(codes[sel] == kh * 3 + kw, g[sel],
+                               torch.zeros_like(g[sel]))
+            h0, w0 = 2 * lo_h - 1 + kh, 2 * lo_w - 1 + kw
+            dst = (slice(None), slice(None),
+                   slice(h0, h0 + 2 * (hi_h - lo_h) + 1, 2),
+                   slice(w0, w0 + 2 * (hi_w - lo_w) + 1, 2))
+            full[dst] = full[dst] + part
+    full = full.to(input.dtype)
+    if input.is_contiguous(memory_format=torch.channels_last):
+        full = full.contiguous(memory_format=torch.channels_last)
+    return full
+
+
+def batch_norm_backward_reduce_act_pool(
+    grad_out, grad_out2, codes, input, mean, invstd, weight, bias, relu_mask,
+    input_g, weight_g, bias_g, negative_slope: float = 0.0,
+):
+    g = pool_gather_grad(grad_out, grad_out2, codes, input)
+    return batch_norm_backward_reduce_act(
+        g, input, None, mean, invstd, weight, bias, relu_mask, input_g,
+        weight_g, bias_g, None, negative_slope,
+    )
+
+
+def batch_norm_backward_elemt_act_pool(
+    grad_out, grad_out2, codes, input, mean, invstd, weight, bias, sum_dy,
+    sum_dy_xmu, count, relu_mask, negative_slope: float = 0.0,
+):
+    g = pool_gather_grad(grad_out, grad_out2, codes, input)
+    return batch_norm_backward_elemt_act(
+        g, input, None, mean, invstd, weight, bias, sum_dy, sum_dy_xmu,
+        count, relu_mask, False, negative_slope,
+    )[0]
+
+
 # ---- in-place activated path ----------------------------------------------
 # fp32 throughout, in the kernels' order of operations: these are the CPU
 # execution path of the in-place ops, and they really overwrite ``input``.

@@ -1574,6 +1574,343 @@ __global__ void bn_bwd_elemt_inplace_nhwc(const T* __restrict__ dy,
 }
 
 // =====================================================================
+// stem pool fusion: bn + act + MaxPool2d(3, 2, 1) without the full-size
+// activation (docs/KERNEL_DESIGN.md "Stem pool fusion").  Channels-last only.
+//
+// Forward: one thread per pooled (n, oh, ow, channel pack) forms
+// y = from_f<T>(act(scale*x + shift)) for the up to nine x packs of its
+// window (rows / columns outside the image are skipped, not read as zero),
+// takes the maximum over the T-ROUNDED y with the stock rule
+// `val > max || isnan(val)` scanning kh then kw ascending (first maximum
+// wins), and stores the pooled pack plus one byte per element, the window
+// code kh*3 + kw.  y itself is never written.
+//
+// Backward: the full-size gradient the stock pool backward would have stored
+// is re-formed per x element by a gather (pool_gather): an element lies in
+// 1, 2 or 4 windows (even h / w: one window row / column, odd: two); each
+// candidate window in ascending (oh, ow) order whose code names this element
+// adds its pooled gradient in fp32, and the sum is rounded to T once -- what
+// max_pool_backward_nhwc<T, float> stored.  With DY2 a window's gradient is
+// fork_grad(dy, dy2), the eager add's result.  The reduce kernel keeps
+// bn_bwd_reduce_partial_nhwc's traversal of x's rows, accumulators, flush
+// period, LDS tree and workspace layout, so its sums are that kernel's sums
+// bit for bit; the elementwise kernel gathers again rather than paying a gm
+// round trip (0.6A of mostly cached reads against 2A).
+// =====================================================================
+// Window / gather reads are shared by neighbouring threads (a pooled window
+// overlaps its neighbours; a pooled gradient is wanted by up to nine x
+// elements).  nt loads skip L1 and are served from L2, plain loads may hit
+// L1.  Measured both ways (profiles/r07_stem_pool.md): plain loads are the
+// faster ones for the forward's window reads and, once the second window
+// column is only read where it exists, for the backward's gather reads.
+// The streamed tensors (x in the backward kernels, every store) stay nt.
+#ifndef MSBN_POOL_FWD_NT
+#define MSBN_POOL_FWD_NT 0
+#endif
+#ifndef MSBN_POOL_GATHER_NT
+#define MSBN_POOL_GATHER_NT 0
+#endif
+
+template <typename T, int V, bool NT>
+__device__ __forceinline__ Pack<T, V> pool_load(const T* p) {
+  if (NT) return nt_load<T, V>(p);
+  return *reinterpret_cast<const Pack<T, V>*>(p);
+}
+
+template <typename T, int V, int ACT>
+__global__ void bn_elemt_pool_nhwc(const T* __restrict__ x,
+                                   T* __restrict__ y,
+                                   uint8_t* __restrict__ codes,
+                                   const float* __restrict__ scale,
+                                   const float* __restrict__ shift,
+                                   int64_t total, int64_t C, int H, int W,
+                                   int OH, int OW, float slope) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+       i * V < total; i += stride) {
+    const int64_t e = i * V;
+    const uint32_t pix = (uint32_t)(e / C);
+    const int64_t c = e - (int64_t)pix * C;
+    const uint32_t t = pix / (uint32_t)OW;
+    const int ow = (int)(pix - t * (uint32_t)OW);
+    const int n = (int)(t / (uint32_t)OH);
+    const int oh = (int)(t - (uint32_t)n * (uint32_t)OH);
+    const int h0 = 2 * oh - 1, w0 = 2 * ow - 1;
+    Pack<float, V> ps, pb;
+    if (V == 1) {
+      ps.v[0] = scale[c];
+      pb.v[0] = shift[c];
+    } else {
+      ps = *reinterpret_cast<const Pack<float, V>*>(&scale[c]);
+      pb = *reinterpret_cast<const Pack<float, V>*>(&shift[c]);
+    }
+    float best[V];
+    uint8_t code[V];
+    // first window position inside the image: what an all -inf window keeps
+    const uint8_t first = (uint8_t)((h0 < 0 ? 3 : 0) + (w0 < 0 ? 1 : 0));
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+      best[k] = -INFINITY;
+      code[k] = first;
+    }
+#pragma unroll
+    for (int kh = 0; kh < 3; ++kh) {
+      const int h = h0 + kh;
+      if (h < 0 || h >= H) continue;
+#pragma unroll
+      for (int kw = 0; kw < 3; ++kw) {
+        const int w = w0 + kw;
+        if (w < 0 || w >= W) continue;
+        const int64_t off = (((int64_t)n * H + h) * W + w) * C + c;
+        const Pack<T, V> px = pool_load<T, V, MSBN_POOL_FWD_NT>(&x[off]);
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+          float z = to_f(px.v[k]) * ps.v[k] + pb.v[k];
+          z = act_fwd<ACT>(z, slope);
+          const float val = to_f(from_f<T>(z));
+          if (val > best[k] || val != val) {
+            best[k] = val;
+            code[k] = (uint8_t)(kh * 3 + kw);
+          }
+        }
+      }
+    }
+    Pack<T, V> py;
+    Pack<uint8_t, V> pc;
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+      py.v[k] = from_f<T>(best[k]);
+      pc.v[k] = code[k];
+    }
+    nt_store<T, V>(&y[e], py);
+    nt_store<uint8_t, V>(&codes[e], pc);
+  }
+}
+
+// The stock pool backward's gradient at x element (n, h, w, c..c+V), in fp32
+// after its one rounding to T.
+template <typename T, int V, bool DY2>
+__device__ __forceinline__ void pool_gather(const T* __restrict__ dy,
+                                            const T* __restrict__ dy2,
+                                            const uint8_t* __restrict__ codes,
+                                            int n, int h, int w, int64_t c,
+                                            int64_t C, int OH, int OW,
+                                            float (&g)[V]) {
+#pragma unroll
+  for (int k = 0; k < V; ++k) g[k] = 0.f;
+  const int oh0 = h >> 1, ow0 = w >> 1;
+  // the window row loop branches (h is all but uniform across a wave); the
+  // second window column is read only by the odd-w lanes that lie in it and
+  // carries a code no window stores everywhere else
+  const int noh = ((h & 1) && oh0 + 1 < OH) ? 2 : 1;
+  const bool two_w = (w & 1) && ow0 + 1 < OW;
+  const int ow1 = two_w ? ow0 + 1 : ow0;
+  const int kw0 = w - (2 * ow0 - 1);
+  for (int a = 0; a < noh; ++a) {
+    const int oh = oh0 + a;
+    const int kh3 = (h - (2 * oh - 1)) * 3;
+    const uint8_t want0 = (uint8_t)(kh3 + kw0);
+    const uint8_t want1 = two_w ? (uint8_t)kh3 : (uint8_t)0xff;  // kw = 0
+    const int64_t row = ((int64_t)n * OH + oh) * OW;
+    const int64_t off0 = (row + ow0) * C + c;
+    const int64_t off1 = (row + ow1) * C + c;
+    constexpr bool GNT = MSBN_POOL_GATHER_NT;
+    const Pack<uint8_t, V> pc0 = pool_load<uint8_t, V, GNT>(&codes[off0]);
+    const Pack<T, V> pg0 = pool_load<T, V, GNT>(&dy[off0]);
+    Pack<T, V> ph0, ph1;
+    if (DY2) ph0 = pool_load<T, V, GNT>(&dy2[off0]);
+    Pack<uint8_t, V> pc1;
+    Pack<T, V> pg1;
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+      pc1.v[k] = 0xff;
+      pg1.v[k] = from_f<T>(0.f);
+      if (DY2) ph1.v[k] = from_f<T>(0.f);
+    }
+    if (two_w) {
+      pc1 = pool_load<uint8_t, V, GNT>(&codes[off1]);
+      pg1 = pool_load<T, V, GNT>(&dy[off1]);
+      if (DY2) ph1 = pool_load<T, V, GNT>(&dy2[off1]);
+    }
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+      const float g0 = DY2 ? fork_grad(pg0.v[k], ph0.v[k]) : to_f(pg0.v[k]);
+      const float g1 = DY2 ? fork_grad(pg1.v[k], ph1.v[k]) : to_f(pg1.v[k]);
+      if (pc0.v[k] == want0) g[k] += g0;
+      if (pc1.v[k] == want1) g[k] += g1;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < V; ++k) g[k] = to_f(from_f<T>(g[k]));
+}
+
+// bn_bwd_reduce_partial_nhwc<T, V, ACT, false, false, false> over x's rows
+// with the dy load replaced by pool_gather.
+template <typename T, int V, int ACT, bool DY2>
+__global__ void bn_bwd_reduce_pool_partial_nhwc(
+    const T* __restrict__ dy, const T* __restrict__ dy2,
+    const uint8_t* __restrict__ codes, const T* __restrict__ x,
+    const float* __restrict__ mean, const float* __restrict__ scale,
+    const float* __restrict__ shift, double* __restrict__ ws, int64_t rows,
+    int64_t C, int64_t chunk_rows, int lpr, int H, int W, int OH, int OW,
+    float slope) {
+  const int rpi = blockDim.x / lpr;
+  const int lane = threadIdx.x % lpr;
+  const int rowoff = threadIdx.x / lpr;
+  const bool active = rowoff < rpi;
+  const int64_t c = (int64_t)blockIdx.x * lpr * V + (int64_t)lane * V;
+  const bool inb = active && (c + V <= C);
+
+  AccPair acc[V];
+  float m[V], scv[V], shv[V];
+#pragma unroll
+  for (int k = 0; k < V; ++k) m[k] = scv[k] = shv[k] = 0.f;
+  if (inb) {
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+      m[k] = mean[c + k];
+      if (ACT) {
+        scv[k] = scale[c + k];
+        shv[k] = shift[c + k];
+      }
+    }
+    const int64_t r0 = (int64_t)blockIdx.y * chunk_rows;
+    const int64_t r1 = i64min(r0 + chunk_rows, rows);
+    // (n, h, w) of row r, stepped along with r (rows < 2^31, host-checked)
+    int n = 0, h = 0, w = 0;
+    if (r0 + rowoff < r1) {
+      const uint32_t r = (uint32_t)(r0 + rowoff);
+      const uint32_t t = r / (uint32_t)W;
+      w = (int)(r - t * (uint32_t)W);
+      n = (int)(t / (uint32_t)H);
+      h = (int)(t - (uint32_t)n * (uint32_t)H);
+    }
+    int since_flush = 0;
+    for (int64_t r = r0 + rowoff; r < r1; r += rpi) {
+      float g[V];
+      pool_gather<T, V, DY2>(dy, dy2, codes, n, h, w, c, C, OH, OW, g);
+      Pack<T, V> px = nt_load<T, V>(&x[r * C + c]);
+#pragma unroll
+      for (int k = 0; k < V; ++k) {
+        const float xv = to_f(px.v[k]);
+        if (ACT) {
+          float z = scv[k] * xv + shv[k];
+          g[k] = act_gate<ACT>(z, g[k], slope);
+        }
+        acc[k].add2(g[k], g[k] * (xv - m[k]));
+      }
+      if (++since_flush == MSBN_ACC_FLUSH) {
+#pragma unroll
+        for (int k = 0; k < V; ++k) acc[k].flush();
+        since_flush = 0;
+      }
+      w += rpi;
+      while (w >= W) {
+        w -= W;
+        if (++h == H) {
+          h = 0;
+          ++n;
+        }
+      }
+    }
+  }
+  double a[V], b[V];
+#pragma unroll
+  for (int k = 0; k < V; ++k) {
+    acc[k].flush();
+    a[k] = acc[k].a;
+    b[k] = acc[k].b;
+  }
+  // LDS tree and workspace layout of bn_bwd_reduce_partial_nhwc
+  __shared__ double sdata[MSBN_BLOCK * V * 2];
+#pragma unroll
+  for (int k = 0; k < V; ++k) {
+    sdata[k * MSBN_BLOCK + threadIdx.x] = a[k];
+    sdata[(V + k) * MSBN_BLOCK + threadIdx.x] = b[k];
+  }
+  for (int st = 1; st < rpi; st <<= 1) {
+    __syncthreads();
+    if (active && (rowoff & ((st << 1) - 1)) == 0 && rowoff + st < rpi) {
+      const int other = threadIdx.x + st * lpr;
+#pragma unroll
+      for (int k = 0; k < V; ++k) {
+        sdata[k * MSBN_BLOCK + threadIdx.x] += sdata[k * MSBN_BLOCK + other];
+        sdata[(V + k) * MSBN_BLOCK + threadIdx.x] +=
+            sdata[(V + k) * MSBN_BLOCK + other];
+      }
+    }
+  }
+  __syncthreads();
+  if (rowoff == 0 && c < C) {
+    const int64_t chunk = blockIdx.y;
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+      if (c + k < C) {
+        double* out = ws + ((c + k) * gridDim.y + chunk) * 2;
+        out[0] = sdata[k * MSBN_BLOCK + threadIdx.x];
+        out[1] = sdata[(V + k) * MSBN_BLOCK + threadIdx.x];
+      }
+    }
+  }
+}
+
+// bn_bwd_elemt_nhwc<T, V, ACT, false, false> with the dy load replaced by
+// pool_gather: reads x, the pooled gradient(s) and the codes, writes dx.
+template <typename T, int V, int ACT, bool DY2>
+__global__ void bn_bwd_elemt_pool_nhwc(
+    const T* __restrict__ dy, const T* __restrict__ dy2,
+    const uint8_t* __restrict__ codes, const T* __restrict__ x,
+    T* __restrict__ dx, const float* __restrict__ ca,
+    const float* __restrict__ cb, const float* __restrict__ cd,
+    const float* __restrict__ scale, const float* __restrict__ shift,
+    int64_t total, int64_t C, int H, int W, int OH, int OW, float slope) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+       i * V < total; i += stride) {
+    const int64_t e = i * V;
+    const uint32_t pix = (uint32_t)(e / C);
+    const int64_t c = e - (int64_t)pix * C;
+    const uint32_t t = pix / (uint32_t)W;
+    const int w = (int)(pix - t * (uint32_t)W);
+    const int n = (int)(t / (uint32_t)H);
+    const int h = (int)(t - (uint32_t)n * (uint32_t)H);
+    float g[V];
+    pool_gather<T, V, DY2>(dy, dy2, codes, n, h, w, c, C, OH, OW, g);
+    if (V == 1) {
+      const float xv = to_f(nt_load1(&x[e]));
+      float gv = g[0];
+      if (ACT) {
+        float z = scale[c] * xv + shift[c];
+        gv = act_gate<ACT>(z, gv, slope);
+      }
+      nt_store1(&dx[e], from_f<T>(ca[c] * gv + cb[c] * xv + cd[c]));
+    } else {
+      Pack<T, V> px = nt_load<T, V>(&x[e]);
+      Pack<float, V> pa = *reinterpret_cast<const Pack<float, V>*>(&ca[c]);
+      Pack<float, V> pb = *reinterpret_cast<const Pack<float, V>*>(&cb[c]);
+      Pack<float, V> pd = *reinterpret_cast<const Pack<float, V>*>(&cd[c]);
+      Pack<float, V> psc, psh;
+      if (ACT) {
+        psc = *reinterpret_cast<const Pack<float, V>*>(&scale[c]);
+        psh = *reinterpret_cast<const Pack<float, V>*>(&shift[c]);
+      }
+      Pack<T, V> po;
+#pragma unroll
+      for (int k = 0; k < V; ++k) {
+        float gv = g[k];
+        const float xv = to_f(px.v[k]);
+        if (ACT) {
+          float z = psc.v[k] * xv + psh.v[k];
+          gv = act_gate<ACT>(z, gv, slope);
+        }
+        po.v[k] = from_f<T>(pa.v[k] * gv + pb.v[k] * xv + pd.v[k]);
+      }
+      nt_store<T, V>(&dx[e], po);
+    }
+  }
+}
+
+// =====================================================================
 // host-side helpers
 // =====================================================================
 
@@ -2533,6 +2870,276 @@ at::Tensor batch_norm_backward_elemt(
 }
 
 // ---------------------------------------------------------------------------
+// stem pool fusion: bn + act + MaxPool2d(3, 2, 1), channels-last
+// ---------------------------------------------------------------------------
+namespace {
+struct PoolGeom {
+  int H, W, OH, OW;
+};
+
+// The pool ops' layout of x: always rows x C.  A 1x1 plane is dense in both
+// formats (get_layout calls it NCHW); its memory is rows x C all the same.
+Layout pool_layout(const at::Tensor& x, const char* op) {
+  TORCH_CHECK(x.dim() == 4 &&
+                  x.is_contiguous(at::MemoryFormat::ChannelsLast),
+              op, ": input must be a dense 4-D channels-last tensor");
+  Layout L{};
+  L.nhwc = true;
+  L.N = x.size(0);
+  L.C = x.size(1);
+  L.S = x.size(2) * x.size(3);
+  L.rows = L.N * L.S;
+  return L;
+}
+
+// geometry of the fixed kernel-3 / stride-2 / padding-1 / floor-mode pool
+PoolGeom pool_geom(const at::Tensor& x, const Layout& L, const char* op) {
+  TORCH_CHECK(L.rows < (int64_t)INT32_MAX, op, ": N*H*W must be below 2^31");
+  PoolGeom g{};
+  g.H = (int)x.size(2);
+  g.W = (int)x.size(3);
+  g.OH = (g.H - 1) / 2 + 1;
+  g.OW = (g.W - 1) / 2 + 1;
+  return g;
+}
+
+void check_pooled(const at::Tensor& t, const at::Tensor& x, const PoolGeom& g,
+                  at::ScalarType dtype, const char* op, const char* what) {
+  TORCH_CHECK(t.dim() == 4 && t.size(0) == x.size(0) &&
+                  t.size(1) == x.size(1) && t.size(2) == g.OH &&
+                  t.size(3) == g.OW && t.scalar_type() == dtype &&
+                  t.device() == x.device() &&
+                  t.is_contiguous(at::MemoryFormat::ChannelsLast),
+              op, ": ", what, " must be a channels-last [N, C, OH, OW] ",
+              dtype, " tensor on the input's device");
+}
+}  // namespace
+
+std::tuple<at::Tensor, at::Tensor> batch_norm_elemt_act_pool(
+    const at::Tensor& input, const c10::optional<at::Tensor>& weight,
+    const c10::optional<at::Tensor>& bias, const at::Tensor& mean,
+    const at::Tensor& invstd, bool relu,
+    const c10::optional<at::Tensor>& coefs_in, double negative_slope) {
+  const Layout L = pool_layout(input, "bn_elemt_pool");
+  TORCH_CHECK(input.numel() > 0, "bn_elemt_pool: empty input");
+  const PoolGeom g = pool_geom(input, L, "bn_elemt_pool");
+  const float slope = (float)negative_slope;
+  const int act = act_mode(relu, slope);
+  auto out = at::empty({input.size(0), L.C, g.OH, g.OW},
+                       input.options().memory_format(
+                           at::MemoryFormat::ChannelsLast));
+  auto codes = at::empty_like(out, out.options().dtype(at::kByte));
+  auto stream = cur_stream();
+  auto coefs = coefs_in.has_value()
+                   ? *coefs_in
+                   : make_fwd_coefs(mean, invstd, weight, bias, L.C);
+  float* scale = coefs.data_ptr<float>();
+  float* shift = scale + L.C;
+  const int64_t total = out.numel();
+  MSBN_DISPATCH_FLOAT_TYPES(input.scalar_type(), "bn_elemt_pool", [&] {
+    const native_t* x =
+        reinterpret_cast<const native_t*>(input.data_ptr<scalar_t>());
+    native_t* y = reinterpret_cast<native_t*>(out.data_ptr<scalar_t>());
+    uint8_t* cp = codes.data_ptr<uint8_t>();
+    constexpr int VMAX = 16 / (int)sizeof(native_t);
+    const ElemtPlan plan =
+        plan_elemt(L, total, (int)sizeof(native_t), {x, y, cp}, scale);
+    MSBN_DISPATCH_V(plan.v, VMAX, [&] {
+      // the dispatcher names widths past 16 B for this type; never chosen
+      constexpr int VK = VV * (int)sizeof(native_t) <= 16 ? VV : 1;
+      MSBN_DISPATCH_ACT(act, ACT_, [&] {
+        hipLaunchKernelGGL((bn_elemt_pool_nhwc<native_t, VK, ACT_>),
+                           dim3(plan.grid), dim3(MSBN_BLOCK), 0, stream, x, y,
+                           cp, scale, shift, total, L.C, g.H, g.W, g.OH, g.OW,
+                           slope);
+      });
+    });
+  });
+  return {out, codes};
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor>
+batch_norm_backward_reduce_act_pool(
+    const at::Tensor& grad_out, const c10::optional<at::Tensor>& grad_out2,
+    const at::Tensor& codes, const at::Tensor& input, const at::Tensor& mean,
+    const at::Tensor& invstd, const c10::optional<at::Tensor>& weight,
+    const c10::optional<at::Tensor>& bias, bool relu_mask, bool input_g,
+    bool weight_g, bool bias_g, const c10::optional<at::Tensor>& coefs_in,
+    double negative_slope) {
+  const Layout L = pool_layout(input, "bn_bwd_reduce_pool");
+  TORCH_CHECK(input.numel() > 0, "bn_bwd_reduce_pool: empty input");
+  const PoolGeom g = pool_geom(input, L, "bn_bwd_reduce_pool");
+  const float slope = (float)negative_slope;
+  const int act = act_mode(relu_mask, slope);
+  check_pooled(grad_out, input, g, input.scalar_type(), "bn_bwd_reduce_pool",
+               "grad_out");
+  const bool has_dy2 = grad_out2.has_value();
+  if (has_dy2)
+    check_pooled(*grad_out2, input, g, input.scalar_type(),
+                 "bn_bwd_reduce_pool", "grad_out2");
+  check_pooled(codes, input, g, at::kByte, "bn_bwd_reduce_pool", "codes");
+  auto f32 = input.options().dtype(at::kFloat);
+  // ONE contiguous buffer for [sum_dy | sum_dy_xmu] -> single all_reduce.
+  auto combined = at::empty({2 * L.C}, f32);
+  auto sum_dy = combined.narrow(0, 0, L.C);
+  auto sum_dy_xmu = combined.narrow(0, L.C, L.C);
+  const auto wtype =
+      weight.has_value() ? weight->scalar_type() : input.scalar_type();
+  auto wopts = input.options().dtype(wtype);
+  at::Tensor grad_weight, grad_bias;
+  if (weight_g) grad_weight = at::empty({L.C}, wopts);
+  if (bias_g) grad_bias = at::empty({L.C}, wopts);
+
+  float* scale = nullptr;
+  float* shift = nullptr;
+  at::Tensor coefs;
+  if (relu_mask) {
+    coefs = coefs_in.has_value()
+                ? *coefs_in
+                : make_fwd_coefs(mean, invstd, weight, bias, L.C);
+    scale = coefs.data_ptr<float>();
+    shift = scale + L.C;
+  }
+
+  auto stream = cur_stream();
+  MSBN_DISPATCH_FLOAT_TYPES(input.scalar_type(), "bn_bwd_reduce_pool", [&] {
+    const native_t* x =
+        reinterpret_cast<const native_t*>(input.data_ptr<scalar_t>());
+    const native_t* dy =
+        reinterpret_cast<const native_t*>(grad_out.data_ptr<scalar_t>());
+    const native_t* dy2 =
+        has_dy2 ? reinterpret_cast<const native_t*>(grad_out2->data_ptr())
+                : nullptr;
+    const uint8_t* cp = codes.data_ptr<uint8_t>();
+    constexpr int VMAX = 16 / (int)sizeof(native_t);
+    // bwd_reduce's plan over x's rows; the pooled tensors and the codes
+    // take part in the vector-width choice
+    const ReducePlan plan =
+        plan_reduce(L, (int)sizeof(native_t), {x, dy, dy2, cp});
+    const int nchunks = plan.nchunks;
+    const auto& ng = plan.nhwc;
+    at::Tensor ws = at::empty({(int64_t)nchunks * L.C * 2},
+                              input.options().dtype(at::kDouble));
+    MSBN_DISPATCH_V(plan.v, VMAX, [&] {
+      // the dispatcher names widths past 16 B for this type; never chosen
+      constexpr int VK = VV * (int)sizeof(native_t) <= 16 ? VV : 1;
+      MSBN_DISPATCH_ACT(act, ACT_, [&] {
+        MSBN_DISPATCH_BOOL(has_dy2, DY2_, [&] {
+          hipLaunchKernelGGL(
+              (bn_bwd_reduce_pool_partial_nhwc<native_t, VK, ACT_, DY2_>),
+              ng.grid, dim3(MSBN_BLOCK), 0, stream, dy, dy2, cp, x,
+              mean.data_ptr<float>(), scale, shift, ws.data_ptr<double>(),
+              L.rows, L.C, ng.chunk_rows, ng.lpr, g.H, g.W, g.OH, g.OW,
+              slope);
+        });
+      });
+    });
+    const int fgrid = (int)cdiv(L.C, kFinalizeWavesPerBlock);
+    MSBN_DISPATCH_RSTAT(wtype, "bn_bwd_reduce_pool", [&] {
+      rstat_t* gw = weight_g ? reinterpret_cast<rstat_t*>(grad_weight.data_ptr())
+                             : nullptr;
+      rstat_t* gb =
+          bias_g ? reinterpret_cast<rstat_t*>(grad_bias.data_ptr()) : nullptr;
+      hipLaunchKernelGGL((bn_bwd_reduce_finalize<rstat_t>), dim3(fgrid),
+                         dim3(MSBN_BLOCK), 0, stream, ws.data_ptr<double>(),
+                         nchunks, L.C, invstd.data_ptr<float>(),
+                         sum_dy.data_ptr<float>(),
+                         sum_dy_xmu.data_ptr<float>(), gw, gb);
+    });
+  });
+  (void)input_g;
+  return {sum_dy, sum_dy_xmu, grad_weight, grad_bias};
+}
+
+at::Tensor batch_norm_backward_elemt_act_pool(
+    const at::Tensor& grad_out, const c10::optional<at::Tensor>& grad_out2,
+    const at::Tensor& codes, const at::Tensor& input, const at::Tensor& mean,
+    const at::Tensor& invstd, const c10::optional<at::Tensor>& weight,
+    const c10::optional<at::Tensor>& bias, const at::Tensor& sum_dy,
+    const at::Tensor& sum_dy_xmu, const at::Tensor& count, bool relu_mask,
+    const c10::optional<at::Tensor>& coefs_in, double negative_slope) {
+  const Layout L = pool_layout(input, "bn_bwd_elemt_pool");
+  TORCH_CHECK(input.numel() > 0, "bn_bwd_elemt_pool: empty input");
+  const PoolGeom g = pool_geom(input, L, "bn_bwd_elemt_pool");
+  const float slope = (float)negative_slope;
+  const int act = act_mode(relu_mask, slope);
+  check_pooled(grad_out, input, g, input.scalar_type(), "bn_bwd_elemt_pool",
+               "grad_out");
+  const bool has_dy2 = grad_out2.has_value();
+  if (has_dy2)
+    check_pooled(*grad_out2, input, g, input.scalar_type(),
+                 "bn_bwd_elemt_pool", "grad_out2");
+  check_pooled(codes, input, g, at::kByte, "bn_bwd_elemt_pool", "codes");
+  auto dx = at::empty_like(input);
+  // total count as a device fp32 scalar (no host sync)
+  at::Tensor count_sum;
+  if (count.numel() == 1 && count.scalar_type() == at::kFloat) {
+    count_sum = count;
+  } else {
+    count_sum = count.to(at::kFloat).sum().reshape({1});
+  }
+  auto stream = cur_stream();
+  auto f32 = input.options().dtype(at::kFloat);
+  auto coefs = at::empty({3 * L.C}, f32);
+  float* ca = coefs.data_ptr<float>();
+  float* cb = ca + L.C;
+  float* cd = cb + L.C;
+  const int cgrid = (int)cdiv(L.C, MSBN_BLOCK);
+  const auto wtype =
+      weight.has_value() ? weight->scalar_type() : at::kFloat;
+  MSBN_DISPATCH_RSTAT(wtype, "bn_bwd_elemt_pool", [&] {
+    const rstat_t* w =
+        weight.has_value()
+            ? reinterpret_cast<const rstat_t*>(weight->data_ptr())
+            : nullptr;
+    hipLaunchKernelGGL((bn_affine_bwd<rstat_t>), dim3(cgrid), dim3(MSBN_BLOCK),
+                       0, stream, mean.data_ptr<float>(),
+                       invstd.data_ptr<float>(), w, sum_dy.data_ptr<float>(),
+                       sum_dy_xmu.data_ptr<float>(),
+                       count_sum.data_ptr<float>(), L.C, ca, cb, cd);
+  });
+  float* scale = nullptr;
+  float* shift = nullptr;
+  at::Tensor fcoefs;
+  if (relu_mask) {
+    fcoefs = coefs_in.has_value()
+                 ? *coefs_in
+                 : make_fwd_coefs(mean, invstd, weight, bias, L.C);
+    scale = fcoefs.data_ptr<float>();
+    shift = scale + L.C;
+  }
+  const int64_t total = input.numel();
+  MSBN_DISPATCH_FLOAT_TYPES(input.scalar_type(), "bn_bwd_elemt_pool", [&] {
+    const native_t* x =
+        reinterpret_cast<const native_t*>(input.data_ptr<scalar_t>());
+    const native_t* dy =
+        reinterpret_cast<const native_t*>(grad_out.data_ptr<scalar_t>());
+    const native_t* dy2 =
+        has_dy2 ? reinterpret_cast<const native_t*>(grad_out2->data_ptr())
+                : nullptr;
+    const uint8_t* cp = codes.data_ptr<uint8_t>();
+    native_t* o = reinterpret_cast<native_t*>(dx.data_ptr<scalar_t>());
+    constexpr int VMAX = 16 / (int)sizeof(native_t);
+    const ElemtPlan plan = plan_elemt(L, total, (int)sizeof(native_t),
+                                      {x, dy, dy2, cp, o}, scale);
+    MSBN_DISPATCH_V(plan.v, VMAX, [&] {
+      // the dispatcher names widths past 16 B for this type; never chosen
+      constexpr int VK = VV * (int)sizeof(native_t) <= 16 ? VV : 1;
+      MSBN_DISPATCH_ACT(act, ACT_, [&] {
+        MSBN_DISPATCH_BOOL(has_dy2, DY2_, [&] {
+          hipLaunchKernelGGL(
+              (bn_bwd_elemt_pool_nhwc<native_t, VK, ACT_, DY2_>),
+              dim3(plan.grid), dim3(MSBN_BLOCK), 0, stream, dy, dy2, cp, x, o,
+              ca, cb, cd, scale, shift, total, L.C, g.H, g.W, g.OH, g.OW,
+              slope);
+        });
+      });
+    });
+  });
+  return dx;
+}
+
+// ---------------------------------------------------------------------------
 // in-place activated path: forward over x, backward from y
 // ---------------------------------------------------------------------------
 namespace {
@@ -3175,9 +3782,12 @@ std::tuple<std::string, std::map<std::string, int64_t>> launch_plan(
     return {"small_plane", d};
   }
 
-  const Layout L = get_layout(input);
+  const bool pool_kind = kind == "elemt_pool" || kind == "bwd_reduce_pool" ||
+                         kind == "bwd_elemt_pool";
+  const Layout L =
+      pool_kind ? pool_layout(input, "launch_plan") : get_layout(input);
   if (kind == "stats" || kind == "bwd_reduce" ||
-      kind == "bwd_reduce_inplace") {
+      kind == "bwd_reduce_inplace" || kind == "bwd_reduce_pool") {
     const ReducePlan p = plan_reduce(L, esize, ptrs);
     path = p.path == RedPath::Nhwc       ? "nhwc"
            : p.path == RedPath::NchwFlat ? "nchw_flat"
@@ -3202,9 +3812,16 @@ std::tuple<std::string, std::map<std::string, int64_t>> launch_plan(
   }
   TORCH_CHECK(kind == "elemt" || kind == "bwd_elemt" ||
                   kind == "frozen_bwd_elemt" || kind == "elemt_inplace" ||
-                  kind == "bwd_elemt_inplace",
+                  kind == "bwd_elemt_inplace" || kind == "elemt_pool" ||
+                  kind == "bwd_elemt_pool",
               "launch_plan: unknown kind '", kind, "'");
-  const ElemtPlan p = plan_elemt(L, input.numel(), esize, ptrs, coef);
+  // elemt_pool threads walk the POOLED tensor, one pack of it each
+  int64_t total = input.numel();
+  if (kind == "elemt_pool") {
+    const PoolGeom g = pool_geom(input, L, "launch_plan");
+    total = input.size(0) * L.C * g.OH * g.OW;
+  }
+  const ElemtPlan p = plan_elemt(L, total, esize, ptrs, coef);
   path = L.nhwc ? "nhwc" : (p.v == 1 ? "nchw_flat" : "nchw_vec");
   const int64_t threads = (int64_t)p.grid * MSBN_BLOCK;
   d["V"] = p.v;

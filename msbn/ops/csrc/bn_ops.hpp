@@ -175,6 +175,44 @@ std::tuple<at::Tensor, at::Tensor> batch_norm_backward_elemt_act(
     bool want_res_grad, const c10::optional<at::Tensor>& coefs_in,
     double negative_slope);
 
+// ---- stem pool fusion: bn + act + MaxPool2d(3, 2, 1) -----------------------
+// Channels-last 4-D input only; the pool geometry is fixed (kernel 3,
+// stride 2, padding 1, dilation 1, floor mode: OH = (H-1)/2 + 1).  The
+// forward returns (pooled, codes): pooled = maxpool(act(x*scale + shift))
+// with the maximum taken over the values rounded to the input dtype, and one
+// uint8 window code kh*3 + kw per pooled element (first maximum in kh, kw
+// order, NaN wins), both channels-last [N, C, OH, OW].  The activation
+// tensor itself is never stored.  The backward ops take the POOLED
+// gradient(s) and the codes in the place of batch_norm_backward_*_act's
+// grad_out: each x element's gradient is gathered from the windows that
+// chose it (fp32 sum in ascending window order, rounded to the input dtype
+// once -- the tensor the pool's own backward would have stored).  grad_out2
+// is the second gradient of a forked pooled output, as in
+// batch_norm_backward_reduce_act.  Results are bit-identical to the unfused
+// composition.
+std::tuple<at::Tensor, at::Tensor> batch_norm_elemt_act_pool(
+    const at::Tensor& input, const c10::optional<at::Tensor>& weight,
+    const c10::optional<at::Tensor>& bias, const at::Tensor& mean,
+    const at::Tensor& invstd, bool relu,
+    const c10::optional<at::Tensor>& coefs_in, double negative_slope);
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor>
+batch_norm_backward_reduce_act_pool(
+    const at::Tensor& grad_out, const c10::optional<at::Tensor>& grad_out2,
+    const at::Tensor& codes, const at::Tensor& input, const at::Tensor& mean,
+    const at::Tensor& invstd, const c10::optional<at::Tensor>& weight,
+    const c10::optional<at::Tensor>& bias, bool relu_mask, bool input_g,
+    bool weight_g, bool bias_g, const c10::optional<at::Tensor>& coefs_in,
+    double negative_slope);
+
+at::Tensor batch_norm_backward_elemt_act_pool(
+    const at::Tensor& grad_out, const c10::optional<at::Tensor>& grad_out2,
+    const at::Tensor& codes, const at::Tensor& input, const at::Tensor& mean,
+    const at::Tensor& invstd, const c10::optional<at::Tensor>& weight,
+    const c10::optional<at::Tensor>& bias, const at::Tensor& sum_dy,
+    const at::Tensor& sum_dy_xmu, const at::Tensor& count, bool relu_mask,
+    const c10::optional<at::Tensor>& coefs_in, double negative_slope);
+
 // ---- in-place activated path (forward over x, backward from y) ------------
 // The forward writes y = act(x*scale + shift) over `input` and returns it;
 // the backward ops take that stored y instead of x and invert the activation
@@ -221,6 +259,10 @@ at::Tensor batch_norm_backward_elemt_inplace(
 //   "elemt_inplace"      input = x,      coefs
 //   "bwd_reduce_inplace" input = y,      others = {grad_out}
 //   "bwd_elemt_inplace"  input = y,      others = {grad_out}
+//   "elemt_pool"         input = x,      others = {pooled, codes}, coefs
+//   "bwd_reduce_pool"    input = x,      others = {grad_out, grad_out2, codes}
+//   "bwd_elemt_pool"     input = x,      others = {grad_out, grad_out2, codes},
+//                                        coefs
 // (pass only what the op itself would dereference).  Returns (path, numbers):
 // path is "nchw_vec" | "nchw_flat" | "nhwc" | "small_plane" | "ineligible";
 // numbers always hold V and trips (most loop iterations of one thread);

@@ -103,6 +103,10 @@ template <>
 struct NTVec<2> {
   using type = short;
 };
+template <>
+struct NTVec<1> {  // one pool window code (scalar path)
+  using type = char;
+};
 
 template <typename T, int V>
 __device__ __forceinline__ Pack<T, V> nt_load(const T* p) {

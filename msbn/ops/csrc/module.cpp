@@ -63,6 +63,25 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("relu_mask"), py::arg("want_res_grad"),
         py::arg("coefs") = py::none(), py::arg("negative_slope") = 0.0);
 
+  m.def("batch_norm_elemt_act_pool", &msbn::batch_norm_elemt_act_pool,
+        py::arg("input"), py::arg("weight"), py::arg("bias"), py::arg("mean"),
+        py::arg("invstd"), py::arg("relu"), py::arg("coefs") = py::none(),
+        py::arg("negative_slope") = 0.0);
+  m.def("batch_norm_backward_reduce_act_pool",
+        &msbn::batch_norm_backward_reduce_act_pool, py::arg("grad_out"),
+        py::arg("grad_out2"), py::arg("codes"), py::arg("input"),
+        py::arg("mean"), py::arg("invstd"), py::arg("weight"), py::arg("bias"),
+        py::arg("relu_mask"), py::arg("input_g"), py::arg("weight_g"),
+        py::arg("bias_g"), py::arg("coefs") = py::none(),
+        py::arg("negative_slope") = 0.0);
+  m.def("batch_norm_backward_elemt_act_pool",
+        &msbn::batch_norm_backward_elemt_act_pool, py::arg("grad_out"),
+        py::arg("grad_out2"), py::arg("codes"), py::arg("input"),
+        py::arg("mean"), py::arg("invstd"), py::arg("weight"), py::arg("bias"),
+        py::arg("sum_dy"), py::arg("sum_dy_xmu"), py::arg("count"),
+        py::arg("relu_mask"), py::arg("coefs") = py::none(),
+        py::arg("negative_slope") = 0.0);
+
   m.def("batch_norm_elemt_act_", &msbn::batch_norm_elemt_act_,
         py::arg("input"), py::arg("weight"), py::arg("bias"), py::arg("mean"),
         py::arg("invstd"), py::arg("act"), py::arg("coefs") = py::none(),
