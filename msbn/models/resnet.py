@@ -56,7 +56,7 @@ class BasicBlock(nn.Module):
     expansion = 1
 
     def __init__(self, cin, planes, stride=1, downsample=None, fused=False,
-                 fork=False):
+                 fork=False, gate_bits=True):
         super().__init__()
         self.fused = fused
         # fused only: return the output as a (main, skip) pair (see _last_bn);
@@ -67,7 +67,10 @@ class BasicBlock(nn.Module):
         self.downsample = downsample
         if fused:
             self.bn1 = SyncBatchNormAct2d(planes, relu=True)
-            self.bn2 = SyncBatchNormAct2d(planes, relu=True)  # takes residual
+            # takes the residual; gate_bits: its backward reads one stored
+            # bit per element where it re-read the residual (fused.py)
+            self.bn2 = SyncBatchNormAct2d(planes, relu=True,
+                                          gate_bits=gate_bits)
         else:
             self.bn1 = BatchNorm2d(planes)
             self.bn2 = BatchNorm2d(planes)
@@ -90,7 +93,7 @@ class Bottleneck(nn.Module):
     expansion = 4
 
     def __init__(self, cin, planes, stride=1, downsample=None, fused=False,
-                 fork=False):
+                 fork=False, gate_bits=True):
         super().__init__()
         self.fused = fused
         self.fork = fork and fused  # as in BasicBlock
@@ -101,7 +104,8 @@ class Bottleneck(nn.Module):
         if fused:
             self.bn1 = SyncBatchNormAct2d(planes, relu=True)
             self.bn2 = SyncBatchNormAct2d(planes, relu=True)
-            self.bn3 = SyncBatchNormAct2d(planes * self.expansion, relu=True)
+            self.bn3 = SyncBatchNormAct2d(planes * self.expansion, relu=True,
+                                          gate_bits=gate_bits)  # as BasicBlock
         else:
             self.bn1 = BatchNorm2d(planes)
             self.bn2 = BatchNorm2d(planes)
@@ -132,9 +136,14 @@ class ResNet(nn.Module):
         in_chans: int = 3,
         fused: bool = False,
         fork_grads: bool = True,
+        gate_bits: bool = True,
     ):
         super().__init__()
         self.fused = fused
+        # fused models: each block's closing BN keeps its activation gate as
+        # one bit per element instead of re-reading the residual in backward.
+        # Same math either way; False keeps the recomputing route.
+        self.gate_bits = gate_bits and fused
         # fused models: every block whose output feeds another block hands
         # it over as a (main, skip) pair (_last_bn).  Same math either way;
         # False keeps autograd's own gradient add at each fork.
@@ -172,11 +181,12 @@ class ResNet(nn.Module):
                 _norm(planes * block.expansion, self.fused),
             )
         layers = [block(self.inplanes, planes, stride, downsample,
-                        fused=self.fused, fork=fork[0])]
+                        fused=self.fused, fork=fork[0],
+                        gate_bits=self.gate_bits)]
         self.inplanes = planes * block.expansion
         for i in range(1, blocks):
             layers.append(block(self.inplanes, planes, fused=self.fused,
-                                fork=fork[i]))
+                                fork=fork[i], gate_bits=self.gate_bits))
         return nn.Sequential(*layers)
 
     def _stem(self, x):
@@ -213,12 +223,12 @@ class ResNet(nn.Module):
 
 
 def resnet18(num_classes: int = 1000, fused: bool = False,
-             fork_grads: bool = True) -> ResNet:
+             fork_grads: bool = True, gate_bits: bool = True) -> ResNet:
     return ResNet(BasicBlock, [2, 2, 2, 2], num_classes, fused=fused,
-                  fork_grads=fork_grads)
+                  fork_grads=fork_grads, gate_bits=gate_bits)
 
 
 def resnet50(num_classes: int = 1000, fused: bool = False,
-             fork_grads: bool = True) -> ResNet:
+             fork_grads: bool = True, gate_bits: bool = True) -> ResNet:
     return ResNet(Bottleneck, [3, 4, 6, 3], num_classes, fused=fused,
-                  fork_grads=fork_grads)
+                  fork_grads=fork_grads, gate_bits=gate_bits)

@@ -7,6 +7,9 @@ modules, but executed as ONE elementwise kernel forward and mask-recomputing
 kernels backward (no clamp / add / threshold_backward kernels, no stored mask,
 ~3x fewer full-tensor round trips on the BN backward — see
 profiles/r01_single_gpu.md for the measured eager-kernel cost this removes).
+A layer with a residual may instead keep one bit per element for its gate
+(``gate_bits``, profiles/r08_gate_bits.md): an eighth of a byte read back
+where the backward re-read the whole residual.
 
 ``SyncBatchNormAct2d`` is used directly by the fused model variants
 (msbn.models.resnet{18,50}(fused=True)); ``convert_sync_batchnorm`` leaves it
@@ -42,6 +45,7 @@ class SyncBatchNormActFunction(torch.autograd.Function):
         relu: bool,
         negative_slope: float = 0.0,
         fork: bool = False,
+        gate_bits: bool = False,
     ):
         """``fork=True`` returns the output twice — ``(y, y.detach())``, two
         tensor objects over one storage, no copy — for a result that feeds
@@ -49,8 +53,17 @@ class SyncBatchNormActFunction(torch.autograd.Function):
         sums gradients per output edge, so two outputs are what lets
         ``backward`` receive the two gradients UNSUMMED and read both inside
         the reduce kernel instead of paying for an eager add (read 2A, write
-        1A) whose only reader is that kernel."""
+        1A) whose only reader is that kernel.
+
+        ``gate_bits=True``: an activated layer whose residual needs its
+        gradient keeps the activation's branch as one bit per element,
+        stored by the forward kernel, instead of the residual tensor: the
+        backward reduce reads numel/8 bytes where it read the residual, and
+        the residual is not saved.  Only the two-stage GPU kernels do this,
+        and only when the forward kernel reports that it stored the bits;
+        every other case saves the residual as before.  Same results."""
         ctx.fork = fork
+        ctx.gate_bits = gate_bits
         y = SyncBatchNormActFunction._forward(
             ctx, input, residual, weight, bias, running_mean, running_var,
             eps, momentum, process_group, world_size, relu, negative_slope,
@@ -66,6 +79,8 @@ class SyncBatchNormActFunction(torch.autograd.Function):
                  running_var, eps, momentum, process_group, world_size, relu,
                  negative_slope):
         ctx.negative_slope = negative_slope
+        ctx.has_res = residual is not None
+        ctx.has_gate = False
         input = _contig(input)
         if residual is not None:
             residual = _match_layout(residual, input)
@@ -108,39 +123,50 @@ class SyncBatchNormActFunction(torch.autograd.Function):
             input, eps, momentum, running_mean, running_var,
             process_group, world_size, weight, bias, want_coefs=True,
         )
-        if coefs is None:
-            ctx.save_for_backward(input, residual, weight, bias, mean, invstd,
-                                  count_sum)
-            ctx.has_coefs = False
-        else:
-            ctx.save_for_backward(input, residual, weight, bias, mean, invstd,
-                                  count_sum, coefs)
-            ctx.has_coefs = True
+        ctx.has_coefs = coefs is not None
         ctx.relu = relu
         ctx.process_group = process_group
         ctx.world_size = world_size
         ctx.use_sync = use_sync
+        # Gate bits: asked for only where backward is certain to write gm
+        # (use_gm there: an activation, and a residual that needs its
+        # gradient), and kept only if the kernel stored them.
+        gate = None
         if input.numel() == 0:
-            return torch.empty_like(input)
-        return ops.batch_norm_elemt_act(
-            input, residual, weight, bias, mean, invstd, relu, coefs,
-            negative_slope,
-        )
+            y = torch.empty_like(input)
+        elif (ctx.gate_bits and relu and residual is not None
+                and ctx.needs_input_grad[1] and input.is_cuda):
+            y, gate = ops.batch_norm_elemt_act(
+                input, residual, weight, bias, mean, invstd, relu, coefs,
+                negative_slope, ops.gate_bits_empty(input),
+            )
+        else:
+            y = ops.batch_norm_elemt_act(
+                input, residual, weight, bias, mean, invstd, relu, coefs,
+                negative_slope,
+            )
+        ctx.has_gate = gate is not None
+        saved = (input, None if ctx.has_gate else residual, weight, bias,
+                 mean, invstd, count_sum)
+        if ctx.has_coefs:
+            saved += (coefs,)
+        if ctx.has_gate:
+            saved += (gate,)
+        ctx.save_for_backward(*saved)
+        return y
 
     @staticmethod
     def backward(ctx, grad_output, grad_skip=None):
         if grad_output is None:  # fork with only the second output used
             grad_output, grad_skip = grad_skip, None
         if grad_output is None:
-            return (None,) * 13
-        if ctx.has_coefs:
-            (input, residual, weight, bias, mean, invstd, count_sum,
-             coefs) = ctx.saved_tensors
-        else:
-            input, residual, weight, bias, mean, invstd, count_sum = (
-                ctx.saved_tensors
-            )
-            coefs = None
+            return (None,) * 14
+        saved = ctx.saved_tensors
+        input, residual, weight, bias, mean, invstd, count_sum = saved[:7]
+        coefs = saved[7] if ctx.has_coefs else None
+        # gate bits stand in for the residual, which was then not saved
+        gate = saved[-1] if ctx.has_gate else None
+        has_res = ctx.has_res
         # Both gradients of a forked output: the two-stage GPU path hands
         # them to the reduce kernel unsummed (grad_out2); every other path
         # (small-plane kernel, CPU, empty-input rank) starts with the eager
@@ -155,7 +181,7 @@ class SyncBatchNormActFunction(torch.autograd.Function):
         # layer that would not have materialized gm anyway keeps the eager
         # add and its fp32 gate.
         if fold and ctx.relu and ctx.negative_slope != 0.0 and not (
-            residual is not None and ctx.needs_input_grad[1]
+            has_res and ctx.needs_input_grad[1]
         ):
             fold = False
         if grad_skip is not None and not fold:
@@ -169,7 +195,7 @@ class SyncBatchNormActFunction(torch.autograd.Function):
         process_group = ctx.process_group
         world_size = ctx.world_size
         need_input_g = ctx.needs_input_grad[0]
-        need_res_g = residual is not None and ctx.needs_input_grad[1]
+        need_res_g = has_res and ctx.needs_input_grad[1]
         need_weight_g = weight is not None and ctx.needs_input_grad[2]
         need_bias_g = bias is not None and ctx.needs_input_grad[3]
 
@@ -190,7 +216,7 @@ class SyncBatchNormActFunction(torch.autograd.Function):
                 grad_res if need_res_g else None,
                 grad_weight if need_weight_g else None,
                 grad_bias if need_bias_g else None,
-                None, None, None, None, None, None, None, None, None,
+                None, None, None, None, None, None, None, None, None, None,
             )
 
         # Masked-grad materialization: when the residual branch needs its
@@ -202,7 +228,7 @@ class SyncBatchNormActFunction(torch.autograd.Function):
         # kernel is the only place their sum exists, and the elemt pass must
         # not read dy / dy2 again.
         use_gm = fold or (
-            relu and residual is not None and need_res_g and input.is_cuda
+            relu and has_res and need_res_g and input.is_cuda
             and input.numel() > 0
         )
         use_sync = getattr(ctx, "use_sync", world_size > 1)
@@ -223,16 +249,26 @@ class SyncBatchNormActFunction(torch.autograd.Function):
                 torch.empty_like(grad_output) if need_res_g else None,
                 torch.zeros_like(weight) if need_weight_g else None,
                 torch.zeros_like(bias) if need_bias_g else None,
-                None, None, None, None, None, None, None, None, None,
+                None, None, None, None, None, None, None, None, None, None,
             )
         gm = torch.empty_like(grad_output) if use_gm else None
-        sum_dy, sum_dy_xmu, grad_weight, grad_bias = (
-            ops.batch_norm_backward_reduce_act(
-                grad_output, input, residual, mean, invstd, weight, bias,
-                relu, need_input_g, need_weight_g, need_bias_g, coefs, gm,
-                slope, grad_skip,
+        if gate is not None:
+            # the forward asked for bits only where use_gm was certain
+            sum_dy, sum_dy_xmu, grad_weight, grad_bias = (
+                ops.batch_norm_backward_reduce_act(
+                    grad_output, input, None, mean, invstd, weight, bias,
+                    relu, need_input_g, need_weight_g, need_bias_g, coefs, gm,
+                    slope, grad_skip, gate=gate,
+                )
             )
-        )
+        else:
+            sum_dy, sum_dy_xmu, grad_weight, grad_bias = (
+                ops.batch_norm_backward_reduce_act(
+                    grad_output, input, residual, mean, invstd, weight, bias,
+                    relu, need_input_g, need_weight_g, need_bias_g, coefs, gm,
+                    slope, grad_skip,
+                )
+            )
         grad_input = grad_res = None
         if need_input_g or need_res_g:
             if use_sync:
@@ -264,7 +300,7 @@ class SyncBatchNormActFunction(torch.autograd.Function):
             grad_res,
             grad_weight if need_weight_g else None,
             grad_bias if need_bias_g else None,
-            None, None, None, None, None, None, None, None, None,
+            None, None, None, None, None, None, None, None, None, None,
         )
 
 
@@ -592,9 +628,13 @@ class SyncBatchNormAct2d(SyncBatchNorm):
     def __init__(self, num_features, eps=1e-5, momentum=0.1, affine=True,
                  track_running_stats=True, process_group=None, device=None,
                  dtype=None, relu: bool = True, negative_slope: float = 0.0,
-                 inplace: bool = False):
+                 inplace: bool = False, gate_bits: bool = True):
         super().__init__(num_features, eps, momentum, affine,
                          track_running_stats, process_group, device, dtype)
+        # keep the activation's branch as one bit per element instead of the
+        # residual where the kernels can (SyncBatchNormActFunction.forward);
+        # False keeps the residual-recomputing route.  Same results.
+        self.gate_bits = bool(gate_bits)
         self.relu = relu
         self.negative_slope = _check_negative_slope(relu, negative_slope)
         if inplace:
@@ -669,4 +709,6 @@ class SyncBatchNormAct2d(SyncBatchNorm):
             input, residual, self.weight, self.bias, running_mean, running_var,
             self.eps, factor, process_group, world_size, self.relu, slope,
             fork,
+            # default: modules pickled before gate_bits existed
+            getattr(self, "gate_bits", False),
         )

@@ -212,36 +212,63 @@ def bn_make_coefs(mean, invstd, weight, bias):
     return None
 
 
+def gate_bits_empty(input: torch.Tensor) -> torch.Tensor:
+    """An unwritten gate-bit tensor for ``input``: ``ceil(numel/8)`` uint8."""
+    return torch.empty((input.numel() + 7) // 8, dtype=torch.uint8,
+                       device=input.device)
+
+
 def batch_norm_elemt_act(input, residual, weight, bias, mean, invstd,
-                         relu: bool, coefs=None, negative_slope: float = 0.0):
+                         relu: bool, coefs=None, negative_slope: float = 0.0,
+                         gate_out=None):
     """y = act(x*scale + shift [+ residual]); ``relu`` turns the activation
-    on and ``negative_slope`` (only consulted then) makes it a LeakyReLU."""
+    on and ``negative_slope`` (only consulted then) makes it a LeakyReLU.
+
+    ``gate_out`` (``gate_bits_empty(input)``) asks the kernel to also store
+    which branch the activation took, one bit per element: bit ``e & 7`` of
+    byte ``e >> 3`` for the element at storage offset ``e``, set where the
+    backward passes the gradient through (relu: ``not z <= 0``; leaky:
+    ``z > 0``).  The call then returns ``(y, gate)`` with ``gate`` either
+    ``gate_out``, written, or None: the kernels store bits only for an
+    activated layer with a residual running 8 elements per thread (GPU,
+    bf16 / half, C — or the plane, for NCHW — a multiple of 8, 16-byte
+    aligned tensors), and the caller keeps the residual otherwise.  ``y`` is
+    the same with and without ``gate_out``."""
     if input.is_cuda:
-        return _require_hip().batch_norm_elemt_act(
+        y, wrote = _require_hip().batch_norm_elemt_act(
             input, residual, weight, bias, mean, invstd, relu, coefs,
-            negative_slope,
+            negative_slope, gate_out,
         )
-    return _ref.batch_norm_elemt_act(
+        return y if gate_out is None else (y, gate_out if wrote else None)
+    y = _ref.batch_norm_elemt_act(
         input, residual, weight, bias, mean, invstd, relu, negative_slope
     )
+    return y if gate_out is None else (y, None)
 
 
 def batch_norm_backward_reduce_act(grad_out, input, residual, mean, invstd,
                                    weight, bias, relu_mask, input_g, weight_g,
                                    bias_g, coefs=None, gm_out=None,
                                    negative_slope: float = 0.0,
-                                   grad_out2=None):
+                                   grad_out2=None, gate=None):
     """First pass of the fused BN backward.  ``grad_out2`` is the second
     gradient of a forked output, delivered unsummed: the incoming gradient is
     ``grad_out + grad_out2`` rounded to the input dtype once (the tensor an
     eager add would have produced), read inside the reduce kernel instead of
-    in a pass of its own.  It requires ``gm_out``."""
+    in a pass of its own.  It requires ``gm_out``.
+
+    ``gate``: the bits ``batch_norm_elemt_act(gate_out=)`` returned for this
+    layer, passed INSTEAD of ``residual`` (which must be None): the kernel
+    takes the activation's branch from them.  GPU only; requires
+    ``relu_mask`` and ``gm_out``.  Same results as with the residual."""
     if input.is_cuda:
         return _require_hip().batch_norm_backward_reduce_act(
             grad_out, input, residual, mean, invstd, weight, bias, relu_mask,
             input_g, weight_g, bias_g, coefs, gm_out, negative_slope,
-            grad_out2,
+            grad_out2, gate,
         )
+    if gate is not None:
+        raise ValueError("gate bits exist on the GPU path only")
     return _ref.batch_norm_backward_reduce_act(
         grad_out, input, residual, mean, invstd, weight, bias, relu_mask,
         input_g, weight_g, bias_g, gm_out, negative_slope, grad_out2,
@@ -417,8 +444,8 @@ def launch_plan(kind: str, input: torch.Tensor, others=(), coefs=None) -> dict:
     ``kind`` / tensors (pass only what the op itself would dereference):
       ``"stats"``             input = x
       ``"bwd_reduce"``        input = x, others = (grad_out, residual, gm_out,
-                                                   grad_out2)
-      ``"elemt"``             input = x, others = (residual,), coefs
+                                                   grad_out2[, gate])
+      ``"elemt"``             input = x, others = (residual[, gate]), coefs
       ``"bwd_elemt"``         input = x, others = (grad_out, residual), coefs
       ``"frozen_bwd_elemt"``  input = grad_out, others = (x, residual), coefs
       ``"fused_local"``       input = x, others = (residual,)
@@ -435,18 +462,23 @@ def launch_plan(kind: str, input: torch.Tensor, others=(), coefs=None) -> dict:
     ``"small_plane"``, or ``"ineligible"`` for ``fused_local``), ``V`` and
     ``trips`` (the most loop iterations any one thread makes); reductions add
     ``nchunks``, ``flush_every``, ``finalize_trips`` and their chunk sizes,
-    elementwise ops add ``grid``, ``packs`` and ``multi_trip``."""
+    elementwise ops add ``grid``, ``packs`` and ``multi_trip``.  When the
+    tuple has the trailing ``gate`` entry (a gate-bit tensor or None; never
+    counted for alignment), ``gate`` tells whether the gate-bit kernel would
+    run, the activation taken as on."""
     path, numbers = _require_hip().launch_plan(kind, input, list(others), coefs)
     plan = dict(numbers)
     plan["path"] = path
-    if "multi_trip" in plan:
-        plan["multi_trip"] = bool(plan["multi_trip"])
+    for flag in ("multi_trip", "gate"):
+        if flag in plan:
+            plan[flag] = bool(plan[flag])
     return plan
 
 
 __all__ = [
     "hip_available",
     "launch_plan",
+    "gate_bits_empty",
     "bn_frozen_coefs",
     "batch_norm_frozen_backward_elemt",
     "batch_norm_elemt_act_pool",

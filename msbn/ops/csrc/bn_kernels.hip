@@ -445,13 +445,20 @@ __global__ void bn_affine_bwd(const float* __restrict__ mean,
 // (guide G13: fuse into the producing kernel).  ACT is kActNone / kActRelu /
 // kActLeaky (common.hpp); `slope` is only read by the kActLeaky
 // instantiations, so none / relu keep their arithmetic.
+//
+// GATE(V = 8, RES, an activation): the thread also stores the byte of gate
+// bits of its pack (common.hpp), taken from the z it already holds, so the
+// backward reduce can take its branch from the bit and skip the res read.
 // =====================================================================
-template <typename T, int V, int ACT, bool RES>
+template <typename T, int V, int ACT, bool RES, bool GATE>
 __global__ void bn_elemt_nchw(const T* __restrict__ x,
                               const T* __restrict__ res, T* __restrict__ y,
                               const float* __restrict__ scale,
                               const float* __restrict__ shift, int64_t total,
-                              int64_t C, int64_t S, float slope) {
+                              int64_t C, int64_t S, float slope,
+                              unsigned char* __restrict__ gate_out) {
+  static_assert(!GATE || (V == 8 && RES && ACT != kActNone),
+                "gate bits: one byte per 8-pack of a bn+add+act layer");
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
        i * V < total; i += stride) {
@@ -468,24 +475,30 @@ __global__ void bn_elemt_nchw(const T* __restrict__ x,
       Pack<T, V> pr;
       if (RES) pr = nt_load<T, V>(&res[e]);
       Pack<T, V> py;
+      unsigned bits = 0;
 #pragma unroll
       for (int k = 0; k < V; ++k) {
         float z = to_f(px.v[k]) * sc + sh;
         if (RES) z += to_f(pr.v[k]);
+        if (GATE) bits |= (unsigned)act_pass<ACT>(z) << k;
         z = act_fwd<ACT>(z, slope);
         py.v[k] = from_f<T>(z);
       }
       nt_store<T, V>(&y[e], py);
+      if (GATE) gate_store(gate_out, e, bits);
     }
   }
 }
 
-template <typename T, int V, int ACT, bool RES>
+template <typename T, int V, int ACT, bool RES, bool GATE>
 __global__ void bn_elemt_nhwc(const T* __restrict__ x,
                               const T* __restrict__ res, T* __restrict__ y,
                               const float* __restrict__ scale,
                               const float* __restrict__ shift, int64_t total,
-                              int64_t C, float slope) {
+                              int64_t C, float slope,
+                              unsigned char* __restrict__ gate_out) {
+  static_assert(!GATE || (V == 8 && RES && ACT != kActNone),
+                "gate bits: one byte per 8-pack of a bn+add+act layer");
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
        i * V < total; i += stride) {
@@ -503,14 +516,17 @@ __global__ void bn_elemt_nhwc(const T* __restrict__ x,
       Pack<T, V> pr;
       if (RES) pr = nt_load<T, V>(&res[e]);
       Pack<T, V> py;
+      unsigned bits = 0;
 #pragma unroll
       for (int k = 0; k < V; ++k) {
         float z = to_f(px.v[k]) * ps.v[k] + pb.v[k];
         if (RES) z += to_f(pr.v[k]);
+        if (GATE) bits |= (unsigned)act_pass<ACT>(z) << k;
         z = act_fwd<ACT>(z, slope);
         py.v[k] = from_f<T>(z);
       }
       nt_store<T, V>(&y[e], py);
+      if (GATE) gate_store(gate_out, e, bits);
     }
   }
 }
@@ -529,13 +545,20 @@ __global__ void bn_elemt_nhwc(const T* __restrict__ x,
 // add<T> kernel stored (fp32 opmath, round-to-nearest-even), so gm, the
 // sums and everything downstream keep their bits.  Only instantiated with
 // GMOUT: the second pass then reads gm and never needs dy / dy2 again.
+//
+// GATE: the forward stored act_pass(z) as one bit per element (gate bits,
+// common.hpp) and the kernel takes its branch from that bit: it loads the
+// byte its pack lies in instead of the res pack, and neither scale nor
+// shift.  Excludes RES; only instantiated with GMOUT.  Everything after the
+// gate is the code of the recomputing kernels, in their order.
 // =====================================================================
 template <typename T>
 __device__ __forceinline__ float fork_grad(T g1, T g2) {
   return to_f(from_f<T>(to_f(g1) + to_f(g2)));
 }
 
-template <typename T, int V, int ACT, bool RES, bool GMOUT, bool DY2>
+template <typename T, int V, int ACT, bool RES, bool GMOUT, bool DY2,
+          bool GATE>
 __global__ void bn_bwd_reduce_partial_nchw(const T* __restrict__ dy,
                                            const T* __restrict__ dy2,
                                            const T* __restrict__ x,
@@ -546,11 +569,14 @@ __global__ void bn_bwd_reduce_partial_nchw(const T* __restrict__ dy,
                                            const float* __restrict__ shift,
                                            double* __restrict__ ws, int64_t N,
                                            int64_t C, int64_t S, int64_t chunkN,
-                                           int64_t chunkS, float slope) {
+                                           int64_t chunkS, float slope,
+                                           const unsigned char* __restrict__ gate) {
+  static_assert(!GATE || (ACT != kActNone && !RES && GMOUT && V <= 8),
+                "gate bits replace the res read of a gm-writing reduce");
   const int64_t c = blockIdx.x;
   const float m = mean[c];
-  const float sc = ACT ? scale[c] : 0.f;
-  const float sh = ACT ? shift[c] : 0.f;
+  const float sc = (ACT && !GATE) ? scale[c] : 0.f;
+  const float sh = (ACT && !GATE) ? shift[c] : 0.f;
   const int64_t n0 = blockIdx.y * chunkN;
   const int64_t n1 = i64min(n0 + chunkN, N);
   const int64_t s0 = blockIdx.z * chunkS;
@@ -565,7 +591,9 @@ __global__ void bn_bwd_reduce_partial_nchw(const T* __restrict__ dy,
                                   nt_load1(&dy2[base + s]))
                       : to_f(nt_load1(&dy[base + s]));
         const float xv = to_f(nt_load1(&x[base + s]));
-        if (ACT) {
+        if (GATE) {
+          g = act_gate_bit<ACT>(gate_load(gate, base + s) & 1u, g, slope);
+        } else if (ACT) {
           float z = sc * xv + sh;
           if (RES) z += to_f(nt_load1(&res[base + s]));
           g = act_gate<ACT>(z, g, slope);
@@ -585,11 +613,15 @@ __global__ void bn_bwd_reduce_partial_nchw(const T* __restrict__ dy,
         Pack<T, V> pg2, pr, pm;
         if (DY2) pg2 = nt_load<T, V>(&dy2[base + s]);
         if (RES) pr = nt_load<T, V>(&res[base + s]);
+        unsigned bits = 0;
+        if (GATE) bits = gate_load(gate, base + s);
 #pragma unroll
         for (int k = 0; k < V; ++k) {
           float g = DY2 ? fork_grad(pg.v[k], pg2.v[k]) : to_f(pg.v[k]);
           const float xv = to_f(px.v[k]);
-          if (ACT) {
+          if (GATE) {
+            g = act_gate_bit<ACT>((bits >> k) & 1u, g, slope);
+          } else if (ACT) {
             float z = sc * xv + sh;
             if (RES) z += to_f(pr.v[k]);
             g = act_gate<ACT>(z, g, slope);
@@ -617,7 +649,7 @@ __global__ void bn_bwd_reduce_partial_nchw(const T* __restrict__ dy,
   }
 }
 
-template <typename T, int ACT, bool RES, bool GMOUT, bool DY2>
+template <typename T, int ACT, bool RES, bool GMOUT, bool DY2, bool GATE>
 __global__ void bn_bwd_reduce_partial_nchw_flat(
     const T* __restrict__ dy, const T* __restrict__ dy2,
     const T* __restrict__ x,
@@ -625,11 +657,13 @@ __global__ void bn_bwd_reduce_partial_nchw_flat(
     const float* __restrict__ mean,
     const float* __restrict__ scale, const float* __restrict__ shift,
     double* __restrict__ ws, int64_t N, int64_t C, int64_t S,
-    int64_t chunk_len, float slope) {
+    int64_t chunk_len, float slope, const unsigned char* __restrict__ gate) {
+  static_assert(!GATE || (ACT != kActNone && !RES && GMOUT),
+                "gate bits replace the res read of a gm-writing reduce");
   const int64_t c = blockIdx.x;
   const float m = mean[c];
-  const float sc = ACT ? scale[c] : 0.f;
-  const float sh = ACT ? shift[c] : 0.f;
+  const float sc = (ACT && !GATE) ? scale[c] : 0.f;
+  const float sh = (ACT && !GATE) ? shift[c] : 0.f;
   const int64_t NS = N * S;
   const int64_t p0 = (int64_t)blockIdx.y * chunk_len;
   const int64_t p1 = i64min(p0 + chunk_len, NS);
@@ -641,7 +675,9 @@ __global__ void bn_bwd_reduce_partial_nchw_flat(
     float g = DY2 ? fork_grad(nt_load1(&dy[e]), nt_load1(&dy2[e]))
                   : to_f(nt_load1(&dy[e]));
     const float xv = to_f(nt_load1(&x[e]));
-    if (ACT) {
+    if (GATE) {
+      g = act_gate_bit<ACT>(gate_load(gate, e) & 1u, g, slope);
+    } else if (ACT) {
       float z = sc * xv + sh;
       if (RES) z += to_f(nt_load1(&res[e]));
       g = act_gate<ACT>(z, g, slope);
@@ -664,7 +700,8 @@ __global__ void bn_bwd_reduce_partial_nchw_flat(
   }
 }
 
-template <typename T, int V, int ACT, bool RES, bool GMOUT, bool DY2>
+template <typename T, int V, int ACT, bool RES, bool GMOUT, bool DY2,
+          bool GATE>
 __global__ void bn_bwd_reduce_partial_nhwc(const T* __restrict__ dy,
                                            const T* __restrict__ dy2,
                                            const T* __restrict__ x,
@@ -676,7 +713,10 @@ __global__ void bn_bwd_reduce_partial_nhwc(const T* __restrict__ dy,
                                            double* __restrict__ ws,
                                            int64_t rows, int64_t C,
                                            int64_t chunk_rows, int lpr,
-                                           float slope) {
+                                           float slope,
+                                           const unsigned char* __restrict__ gate) {
+  static_assert(!GATE || (ACT != kActNone && !RES && GMOUT && V <= 8),
+                "gate bits replace the res read of a gm-writing reduce");
   const int rpi = blockDim.x / lpr;
   const int lane = threadIdx.x % lpr;
   const int rowoff = threadIdx.x / lpr;
@@ -692,7 +732,7 @@ __global__ void bn_bwd_reduce_partial_nhwc(const T* __restrict__ dy,
 #pragma unroll
     for (int k = 0; k < V; ++k) {
       m[k] = mean[c + k];
-      if (ACT) {
+      if (ACT && !GATE) {
         scv[k] = scale[c + k];
         shv[k] = shift[c + k];
       }
@@ -706,11 +746,15 @@ __global__ void bn_bwd_reduce_partial_nhwc(const T* __restrict__ dy,
       Pack<T, V> pg2, pr, pm;
       if (DY2) pg2 = nt_load<T, V>(&dy2[r * C + c]);
       if (RES) pr = nt_load<T, V>(&res[r * C + c]);
+      unsigned bits = 0;
+      if (GATE) bits = gate_load(gate, r * C + c);
 #pragma unroll
       for (int k = 0; k < V; ++k) {
         float g = DY2 ? fork_grad(pg.v[k], pg2.v[k]) : to_f(pg.v[k]);
         const float xv = to_f(px.v[k]);
-        if (ACT) {
+        if (GATE) {
+          g = act_gate_bit<ACT>((bits >> k) & 1u, g, slope);
+        } else if (ACT) {
           float z = scv[k] * xv + shv[k];
           if (RES) z += to_f(pr.v[k]);
           g = act_gate<ACT>(z, g, slope);
@@ -2524,17 +2568,37 @@ at::Tensor bn_make_coefs(const at::Tensor& mean, const at::Tensor& invstd,
   return make_fwd_coefs(mean, invstd, weight, bias, mean.numel());
 }
 
-at::Tensor batch_norm_elemt_act(const at::Tensor& input,
-                                const c10::optional<at::Tensor>& residual,
-                                const c10::optional<at::Tensor>& weight,
-                                const c10::optional<at::Tensor>& bias,
-                                const at::Tensor& mean,
-                                const at::Tensor& invstd, bool relu,
-                                const c10::optional<at::Tensor>& coefs_in,
-                                double negative_slope) {
+namespace {
+// ceil(numel / 8) dense bytes next to the activation tensor they describe
+void check_gate_tensor(const at::Tensor& gate, const at::Tensor& input,
+                       const char* name) {
+  TORCH_CHECK(gate.scalar_type() == at::kByte && gate.is_contiguous() &&
+                  gate.device() == input.device() &&
+                  gate.numel() == (input.numel() + 7) / 8,
+              name, " must be a contiguous uint8 tensor of ceil(numel/8) "
+              "bytes on the input's device");
+}
+
+// The bit-storing forward kernels exist for an activation, a residual and a
+// pack of 8 (one thread = one byte); anything else declines.
+inline bool elemt_writes_gate(int act, bool has_res, int v) {
+  return act != kActNone && has_res && v == 8;
+}
+}  // namespace
+
+std::tuple<at::Tensor, bool> batch_norm_elemt_act(
+    const at::Tensor& input, const c10::optional<at::Tensor>& residual,
+    const c10::optional<at::Tensor>& weight,
+    const c10::optional<at::Tensor>& bias, const at::Tensor& mean,
+    const at::Tensor& invstd, bool relu,
+    const c10::optional<at::Tensor>& coefs_in, double negative_slope,
+    const c10::optional<at::Tensor>& gate_out) {
   const Layout L = get_layout(input);
   auto out = at::empty_like(input);
-  if (input.numel() == 0) return out;
+  if (gate_out.has_value())
+    check_gate_tensor(*gate_out, input, "gate_out");
+  bool wrote_gate = false;
+  if (input.numel() == 0) return {out, wrote_gate};
   const float slope = (float)negative_slope;
   const int act = act_mode(relu, slope);
   auto stream = cur_stream();
@@ -2564,23 +2628,40 @@ at::Tensor batch_norm_elemt_act(const at::Tensor& input,
         plan_elemt(L, total, (int)sizeof(native_t), {x, y, res}, scale);
     const int v = plan.v;
     const int grid = plan.grid;
+    wrote_gate = gate_out.has_value() && elemt_writes_gate(act, has_res, v);
+    unsigned char* gate =
+        wrote_gate ? gate_out->data_ptr<unsigned char>() : nullptr;
     MSBN_DISPATCH_V(v, VMAX, [&] {
       MSBN_DISPATCH_ACT(act, ACT_, [&] {
         MSBN_DISPATCH_BOOL(has_res, RES_, [&] {
-          if (!L.nhwc) {
-            hipLaunchKernelGGL((bn_elemt_nchw<native_t, VV, ACT_, RES_>),
-                               dim3(grid), dim3(MSBN_BLOCK), 0, stream, x, res,
-                               y, scale, shift, total, L.C, L.S, slope);
+          auto launch = [&](auto gate_c) {
+            constexpr bool GATE_ = decltype(gate_c)::value;
+            if (!L.nhwc) {
+              hipLaunchKernelGGL(
+                  (bn_elemt_nchw<native_t, VV, ACT_, RES_, GATE_>), dim3(grid),
+                  dim3(MSBN_BLOCK), 0, stream, x, res, y, scale, shift, total,
+                  L.C, L.S, slope, gate);
+            } else {
+              hipLaunchKernelGGL(
+                  (bn_elemt_nhwc<native_t, VV, ACT_, RES_, GATE_>), dim3(grid),
+                  dim3(MSBN_BLOCK), 0, stream, x, res, y, scale, shift, total,
+                  L.C, slope, gate);
+            }
+          };
+          // the bit store is compiled for the one combination that can run
+          // it (elemt_writes_gate): 2 dtypes x 2 activations x 2 layouts
+          constexpr bool kCanGate = VV == 8 && sizeof(native_t) == 2 &&
+                                    ACT_ != kActNone && RES_;
+          if (wrote_gate) {
+            launch(std::integral_constant<bool, kCanGate>{});
           } else {
-            hipLaunchKernelGGL((bn_elemt_nhwc<native_t, VV, ACT_, RES_>),
-                               dim3(grid), dim3(MSBN_BLOCK), 0, stream, x, res,
-                               y, scale, shift, total, L.C, slope);
+            launch(std::false_type{});
           }
         });
       });
     });
   });
-  return out;
+  return {out, wrote_gate};
 }
 
 at::Tensor batch_norm_elemt(const at::Tensor& input,
@@ -2589,8 +2670,9 @@ at::Tensor batch_norm_elemt(const at::Tensor& input,
                             const at::Tensor& mean, const at::Tensor& invstd,
                             double eps) {
   (void)eps;  // invstd already folds eps
-  return batch_norm_elemt_act(input, c10::nullopt, weight, bias, mean, invstd,
-                              false, c10::nullopt, 0.0);
+  return std::get<0>(batch_norm_elemt_act(input, c10::nullopt, weight, bias,
+                                          mean, invstd, false, c10::nullopt,
+                                          0.0, c10::nullopt));
 }
 
 std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor>
@@ -2601,10 +2683,21 @@ batch_norm_backward_reduce_act(
     const c10::optional<at::Tensor>& bias, bool relu_mask, bool input_g,
     bool weight_g, bool bias_g, const c10::optional<at::Tensor>& coefs_in,
     const c10::optional<at::Tensor>& gm_out, double negative_slope,
-    const c10::optional<at::Tensor>& grad_out2) {
+    const c10::optional<at::Tensor>& grad_out2,
+    const c10::optional<at::Tensor>& gate) {
   const Layout L = get_layout(input);
   const float slope = (float)negative_slope;
   const int act = act_mode(relu_mask, slope);
+  const bool has_gate = gate.has_value();
+  if (has_gate) {
+    // the bits stand in for the residual: the forward wrote them for an
+    // activated bn+add layer of a 2-byte dtype, and gm carries the result
+    TORCH_CHECK(act != kActNone && !residual.has_value() &&
+                    gm_out.has_value() && input.element_size() == 2,
+                "gate needs relu_mask, gm_out, a bf16 / half input and no "
+                "residual");
+    check_gate_tensor(*gate, input, "gate");
+  }
   if (input.numel() == 0) {
     auto z32 = input.options().dtype(at::kFloat);
     auto combined0 = at::zeros({2 * L.C}, z32);
@@ -2655,13 +2748,16 @@ batch_norm_backward_reduce_act(
   float* scale = nullptr;
   float* shift = nullptr;
   at::Tensor coefs;
-  if (relu_mask) {
+  if (relu_mask && !has_gate) {  // the gate kernels never form z
     coefs = coefs_in.has_value()
                 ? *coefs_in
                 : make_fwd_coefs(mean, invstd, weight, bias, L.C);
     scale = coefs.data_ptr<float>();
     shift = scale + L.C;
   }
+  // byte loads: no alignment demand, so not among plan_reduce's pointers
+  const unsigned char* gate_p =
+      has_gate ? gate->data_ptr<unsigned char>() : nullptr;
 
   auto stream = cur_stream();
   MSBN_DISPATCH_FLOAT_TYPES(input.scalar_type(), "bn_bwd_reduce", [&] {
@@ -2690,27 +2786,32 @@ batch_norm_backward_reduce_act(
         MSBN_DISPATCH_BOOL(want_gm, GM_, [&] {
           // DY2 exists only with GMOUT (has_dy2 implies want_gm, checked
           // above): 3 kernels per (T, V, ACT, RES), not 4
-          auto launch = [&](auto dy2_c) {
+          // GATE likewise only where the checks above let it run (an
+          // activation, GMOUT, no RES, a 2-byte dtype)
+          auto launch = [&](auto dy2_c, auto gate_c) {
             constexpr bool DY2_ = decltype(dy2_c)::value && GM_;
+            constexpr bool GATE_ = decltype(gate_c)::value && GM_ && !RES_ &&
+                                   ACT_ != kActNone && sizeof(native_t) == 2;
             if (!L.nhwc) {
               if (plan.path == RedPath::NchwFlat) {
                 const auto& g = plan.flat;
                 hipLaunchKernelGGL(
                     (bn_bwd_reduce_partial_nchw_flat<native_t, ACT_, RES_,
-                                                     GM_, DY2_>),
+                                                     GM_, DY2_, GATE_>),
                     g.grid, dim3(MSBN_BLOCK), 0, stream, dy, dy2, x, res, gm,
                     mean.data_ptr<float>(), scale, shift,
-                    ws.data_ptr<double>(), L.N, L.C, L.S, g.chunk_len, slope);
+                    ws.data_ptr<double>(), L.N, L.C, L.S, g.chunk_len, slope,
+                    gate_p);
               } else {
                 const auto& g = plan.nchw;
                 MSBN_DISPATCH_V(v, VMAX, [&] {
                   hipLaunchKernelGGL(
                       (bn_bwd_reduce_partial_nchw<native_t, VV, ACT_, RES_,
-                                                  GM_, DY2_>),
+                                                  GM_, DY2_, GATE_>),
                       g.grid, dim3(MSBN_BLOCK), 0, stream, dy, dy2, x, res,
                       gm, mean.data_ptr<float>(), scale, shift,
                       ws.data_ptr<double>(), L.N, L.C, L.S, g.chunkN,
-                      g.chunkS, slope);
+                      g.chunkS, slope, gate_p);
                 });
               }
             } else {
@@ -2718,18 +2819,24 @@ batch_norm_backward_reduce_act(
               MSBN_DISPATCH_V(v, VMAX, [&] {
                 hipLaunchKernelGGL(
                     (bn_bwd_reduce_partial_nhwc<native_t, VV, ACT_, RES_, GM_,
-                                                DY2_>),
+                                                DY2_, GATE_>),
                     g.grid, dim3(MSBN_BLOCK), 0, stream, dy, dy2, x, res, gm,
                     mean.data_ptr<float>(), scale, shift,
                     ws.data_ptr<double>(), L.rows, L.C, g.chunk_rows, g.lpr,
-                    slope);
+                    slope, gate_p);
               });
             }
           };
-          if (has_dy2) {
-            launch(std::true_type{});
+          if (has_gate) {
+            if (has_dy2) {
+              launch(std::true_type{}, std::true_type{});
+            } else {
+              launch(std::false_type{}, std::true_type{});
+            }
+          } else if (has_dy2) {
+            launch(std::true_type{}, std::false_type{});
           } else {
-            launch(std::false_type{});
+            launch(std::false_type{}, std::false_type{});
           }
         });
       });
@@ -2760,7 +2867,7 @@ batch_norm_backward_reduce(const at::Tensor& grad_out, const at::Tensor& input,
                                         invstd, weight, c10::nullopt, false,
                                         input_g, weight_g, bias_g,
                                         c10::nullopt, c10::nullopt, 0.0,
-                                        c10::nullopt);
+                                        c10::nullopt, c10::nullopt);
 }
 
 std::tuple<at::Tensor, at::Tensor> batch_norm_backward_elemt_act(
@@ -3760,9 +3867,17 @@ std::tuple<std::string, std::map<std::string, int64_t>> launch_plan(
               "launch_plan: input must be a non-empty >= 2-D tensor");
   const int esize = (int)input.element_size();
   TORCH_CHECK(esize == 2 || esize == 4, "launch_plan: unsupported dtype");
+  // gate bits: the optional last entry of "elemt" (others[1]) and
+  // "bwd_reduce" (others[4]).  Bytes, so never among the pack pointers.
+  const size_t gate_at = kind == "elemt"        ? 1
+                         : kind == "bwd_reduce" ? 4
+                                                : others.size();
+  auto given = [&](size_t i) {
+    return i < others.size() && others[i].has_value() && others[i]->defined();
+  };
   std::vector<const void*> ptrs{input.data_ptr()};
-  for (const auto& t : others)
-    if (t.has_value() && t->defined()) ptrs.push_back(t->data_ptr());
+  for (size_t i = 0; i < others.size(); ++i)
+    if (i != gate_at && given(i)) ptrs.push_back(others[i]->data_ptr());
   const float* coef = coefs.has_value() && coefs->defined()
                           ? coefs->data_ptr<float>()
                           : nullptr;
@@ -3808,6 +3923,10 @@ std::tuple<std::string, std::map<std::string, int64_t>> launch_plan(
       d["lpr"] = p.nhwc.lpr;
       d["ctiles"] = p.nhwc.grid.x;
     }
+    // would the bit-reading kernel run (batch_norm_backward_reduce_act's
+    // own conditions; the activation is taken as on)
+    if (gate_at < others.size())
+      d["gate"] = given(gate_at) && !given(1) && given(2) && esize == 2;
     return {path, d};
   }
   TORCH_CHECK(kind == "elemt" || kind == "bwd_elemt" ||
@@ -3829,6 +3948,9 @@ std::tuple<std::string, std::map<std::string, int64_t>> launch_plan(
   d["packs"] = p.packs;
   d["trips"] = cdiv(p.packs, threads);
   d["multi_trip"] = p.packs > threads ? 1 : 0;
+  // would the forward store the bits (the activation is taken as on)
+  if (gate_at < others.size())
+    d["gate"] = given(gate_at) && elemt_writes_gate(kActRelu, given(0), p.v);
   return {path, d};
 }
 

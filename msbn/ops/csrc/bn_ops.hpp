@@ -90,20 +90,28 @@ at::Tensor bn_make_coefs(const at::Tensor& mean, const at::Tensor& invstd,
                          const c10::optional<at::Tensor>& weight,
                          const c10::optional<at::Tensor>& bias);
 
-at::Tensor batch_norm_elemt_act(const at::Tensor& input,
-                                const c10::optional<at::Tensor>& residual,
-                                const c10::optional<at::Tensor>& weight,
-                                const c10::optional<at::Tensor>& bias,
-                                const at::Tensor& mean,
-                                const at::Tensor& invstd, bool relu,
-                                const c10::optional<at::Tensor>& coefs_in,
-                                double negative_slope);
+// gate_out: uint8[ceil(numel/8)], bit (e & 7) of byte (e >> 3) = "the
+// activation passes the gradient at storage offset e" (gate bits,
+// docs/KERNEL_DESIGN.md).  The kernels store them only for an activated
+// layer with a residual that runs at 8 elements per thread (bf16 / half,
+// C or S a multiple of 8, 16-byte aligned tensors); the returned flag says
+// whether they did.  y does not depend on gate_out.
+std::tuple<at::Tensor, bool> batch_norm_elemt_act(
+    const at::Tensor& input, const c10::optional<at::Tensor>& residual,
+    const c10::optional<at::Tensor>& weight,
+    const c10::optional<at::Tensor>& bias, const at::Tensor& mean,
+    const at::Tensor& invstd, bool relu,
+    const c10::optional<at::Tensor>& coefs_in, double negative_slope,
+    const c10::optional<at::Tensor>& gate_out);
 
 // grad_out2: second gradient of a forked output (residual block: conv1 and
 // the skip path), delivered unsummed.  The kernel uses
 // round_T(grad_out + grad_out2) as the incoming gradient — bit for bit the
 // tensor an eager add would have stored — without that add's pass over
 // memory.  Requires gm_out (the second pass then reads gm alone).
+// gate: the bits batch_norm_elemt_act stored for this layer, given INSTEAD
+// of its residual: the gate is taken from them, at any pack width.  Requires
+// relu_mask, gm_out and a bf16 / half input.
 std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor>
 batch_norm_backward_reduce_act(
     const at::Tensor& grad_out, const at::Tensor& input,
@@ -112,7 +120,8 @@ batch_norm_backward_reduce_act(
     const c10::optional<at::Tensor>& bias, bool relu_mask, bool input_g,
     bool weight_g, bool bias_g, const c10::optional<at::Tensor>& coefs_in,
     const c10::optional<at::Tensor>& gm_out, double negative_slope,
-    const c10::optional<at::Tensor>& grad_out2);
+    const c10::optional<at::Tensor>& grad_out2,
+    const c10::optional<at::Tensor>& gate);
 
 // ---- frozen path (normalize with running stats, autograd on) --------------
 // One launch: (running_mean, running_var, eps, weight?, bias?) -> packed fp32

@@ -66,13 +66,67 @@ __device__ __forceinline__ float act_fwd(float z, float slope) {
 
 // backward: g = dy * act'(z); z == 0 takes the negative branch in both modes
 // (stock threshold_backward / leaky_relu_backward convention).
+//
+// The branch is ONE predicate, act_pass: the forward may store it as a bit
+// per element (gate bits, docs/KERNEL_DESIGN.md) and the backward then
+// applies act_gate_bit to the stored bit instead of recomputing z, so the two
+// cannot disagree.  A NaN z passes the gradient under relu (`z <= 0` is
+// false) and takes the slope branch under leaky (`z > 0` is false).
+template <int ACT>
+__device__ __forceinline__ bool act_pass(float z) {
+  if (ACT == kActRelu) return !(z <= 0.f);
+  if (ACT == kActLeaky) return z > 0.f;
+  return true;
+}
+
+template <int ACT>
+__device__ __forceinline__ float act_gate_bit(bool pass, float g,
+                                              float slope) {
+  if (ACT == kActRelu) {
+    if (!pass) g = 0.f;
+  }
+  if (ACT == kActLeaky) g = pass ? g : slope * g;
+  return g;
+}
+
 template <int ACT>
 __device__ __forceinline__ float act_gate(float z, float g, float slope) {
-  if (ACT == kActRelu) {
-    if (z <= 0.f) g = 0.f;
-  }
-  if (ACT == kActLeaky) g = z > 0.f ? g : slope * g;
-  return g;
+  return act_gate_bit<ACT>(act_pass<ACT>(z), g, slope);
+}
+
+// ------------------------------------------------------------------ gate bits
+// One bit per element of a dense activation tensor: bit (e & 7) of byte
+// (e >> 3) is act_pass<ACT>(z) of the element at storage offset e.  A V = 8
+// forward thread owns one whole byte; a backward thread of any V <= 8 loads
+// the byte its pack lies in (V divides 8 and e is a multiple of V, so a pack
+// never straddles two bytes).  MSBN_GATE_STORE_NT / MSBN_GATE_LOAD_NT pick
+// nontemporal byte accesses (A/B knobs; the defaults are what measured
+// fastest, profiles/r08_gate_bits.md).
+#ifndef MSBN_GATE_STORE_NT
+#define MSBN_GATE_STORE_NT 0
+#endif
+#ifndef MSBN_GATE_LOAD_NT
+#define MSBN_GATE_LOAD_NT 0
+#endif
+
+__device__ __forceinline__ void gate_store(unsigned char* gate, int64_t e,
+                                           unsigned bits) {
+#if MSBN_GATE_STORE_NT && !defined(MSBN_DISABLE_NT)
+  __builtin_nontemporal_store((unsigned char)bits, &gate[e >> 3]);
+#else
+  gate[e >> 3] = (unsigned char)bits;
+#endif
+}
+
+// the bits of the pack that starts at element e, bit k = element e + k
+__device__ __forceinline__ unsigned gate_load(const unsigned char* gate,
+                                              int64_t e) {
+#if MSBN_GATE_LOAD_NT && !defined(MSBN_DISABLE_NT)
+  const unsigned b = __builtin_nontemporal_load(&gate[e >> 3]);
+#else
+  const unsigned b = gate[e >> 3];
+#endif
+  return b >> (unsigned)(e & 7);
 }
 
 // ------------------------------------------------ nontemporal pack load/store

@@ -47,7 +47,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("batch_norm_elemt_act", &msbn::batch_norm_elemt_act, py::arg("input"),
         py::arg("residual"), py::arg("weight"), py::arg("bias"),
         py::arg("mean"), py::arg("invstd"), py::arg("relu"),
-        py::arg("coefs") = py::none(), py::arg("negative_slope") = 0.0);
+        py::arg("coefs") = py::none(), py::arg("negative_slope") = 0.0,
+        py::arg("gate_out") = py::none());
   m.def("batch_norm_backward_reduce_act",
         &msbn::batch_norm_backward_reduce_act, py::arg("grad_out"),
         py::arg("input"), py::arg("residual"), py::arg("mean"),
@@ -55,7 +56,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("relu_mask"), py::arg("input_g"), py::arg("weight_g"),
         py::arg("bias_g"), py::arg("coefs") = py::none(),
         py::arg("gm_out") = py::none(), py::arg("negative_slope") = 0.0,
-        py::arg("grad_out2") = py::none());
+        py::arg("grad_out2") = py::none(), py::arg("gate") = py::none());
   m.def("batch_norm_backward_elemt_act", &msbn::batch_norm_backward_elemt_act,
         py::arg("grad_out"), py::arg("input"), py::arg("residual"),
         py::arg("mean"), py::arg("invstd"), py::arg("weight"), py::arg("bias"),

@@ -12,6 +12,8 @@ Cases (argv[1]):
            forward/backward must match the local (no-collective) path.
   graph  — whole-step hipGraph capture (fwd+bwd+opt) WITH the RCCL
            collectives inside the graph; replays must track an eager clone.
+  gate   — one bn+add+relu layer under forced sync, gate bits on and off:
+           bit-equal results, the bits saved in place of the residual.
 
 Run standalone (a known ROCm issue segfaults hipGraph capture inside the
 pytest host process — see tests/test_gpu_fused.py::test_graphed_step_gpu).
@@ -210,6 +212,37 @@ def case_stress():
     print("CASE stress OK")
 
 
+def case_gate():
+    """A forced-sync bn+add+relu layer with gate bits and with the residual
+    route: the bits are local, so the collectives see the same bytes and
+    every result is bit-equal."""
+    from msbn.nn.fused import SyncBatchNormAct2d
+
+    cl = torch.channels_last
+    g = torch.Generator(device="cuda").manual_seed(5)
+    x = torch.randn(4, 16, 6, 6, generator=g, device="cuda") \
+        .bfloat16().contiguous(memory_format=cl)
+    r = torch.randn(4, 16, 6, 6, generator=g, device="cuda") \
+        .bfloat16().contiguous(memory_format=cl)
+    dy = torch.randn(4, 16, 6, 6, generator=g, device="cuda") \
+        .bfloat16().contiguous(memory_format=cl)
+    out = []
+    for gate_bits in (True, False):
+        bn = SyncBatchNormAct2d(16, gate_bits=gate_bits).cuda().train()
+        saved = []
+        xi, ri = x.clone().requires_grad_(True), r.clone().requires_grad_(True)
+        with torch.autograd.graph.saved_tensors_hooks(
+                lambda t: saved.append(t) or t, lambda t: t):
+            y = bn(xi, residual=ri)
+        assert any(t.dtype == torch.uint8 for t in saved) == gate_bits
+        y.backward(dy)
+        out.append((y.detach(), xi.grad, ri.grad, bn.weight.grad,
+                    bn.bias.grad, bn.running_mean, bn.running_var))
+    for a, b in zip(*out):
+        assert torch.equal(a, b)
+    print("CASE gate OK")
+
+
 def main():
     case = sys.argv[1] if len(sys.argv) > 1 else "ddp"
     torch.cuda.set_device(0)
@@ -223,6 +256,8 @@ def main():
             case_h2d()
         elif case == "stress":
             case_stress()
+        elif case == "gate":
+            case_gate()
         else:
             raise SystemExit(f"unknown case {case}")
     finally:
