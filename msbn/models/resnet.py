@@ -16,7 +16,8 @@ import torch
 import torch.nn as nn
 
 from msbn.nn import BatchNorm2d, SyncBatchNorm
-from msbn.nn.fused import SyncBatchNormAct2d, bn_act_maxpool
+from msbn.nn.fused import (SyncBatchNormAct2d, bn_act_maxpool,
+                           bn_add_bn_act)
 
 
 def conv3x3(cin, cout, stride=1):
@@ -52,16 +53,55 @@ def _last_bn(bn, x, identity, fork):
     return y, y
 
 
+def _dual_downsample(block):
+    """True when the block's skip path is exactly (Conv2d, SyncBatchNorm)
+    and the dual BN route is asked for: its BatchNorm then runs inside the
+    closing BN's kernels (msbn/nn/fused.py bn_add_bn_act), which falls back
+    to the composition itself for anything it does not take."""
+    d = block.downsample
+    return (
+        block.fused and getattr(block, "dual_bn", False)
+        and type(d) is nn.Sequential and len(d) == 2
+        and type(d[0]) is nn.Conv2d and type(d[1]) is SyncBatchNorm
+        and not (d._forward_hooks or d._forward_pre_hooks
+                 or d._backward_hooks or d._backward_pre_hooks)
+    )
+
+
+def _skip_path(block, skip):
+    """``(identity, x_d)`` of a block.  On the dual route the skip path stops
+    after its conv (where it has always run, ahead of conv1): ``identity`` is
+    None and ``x_d`` goes to ``_close`` unnormalised."""
+    if _dual_downsample(block):
+        return None, block.downsample[0](skip)
+    if block.downsample is not None:
+        return block.downsample(skip), None
+    return skip, None
+
+
+def _close(block, bn, x, identity, x_d):
+    """The block's closing bn(+add)+relu over the conv output ``x``."""
+    fork = getattr(block, "fork", False)
+    if identity is None:
+        if isinstance(bn, SyncBatchNormAct2d):
+            return bn_add_bn_act(bn, block.downsample[1], x, x_d, fork)
+        identity = block.downsample[1](x_d)
+    return _last_bn(bn, x, identity, fork)
+
+
 class BasicBlock(nn.Module):
     expansion = 1
 
     def __init__(self, cin, planes, stride=1, downsample=None, fused=False,
-                 fork=False, gate_bits=True):
+                 fork=False, gate_bits=True, dual_bn=True):
         super().__init__()
         self.fused = fused
         # fused only: return the output as a (main, skip) pair (see _last_bn);
         # off by default, so a stand-alone block maps tensor -> tensor
         self.fork = fork and fused
+        # fused, with a (Conv2d, SyncBatchNorm) downsample: its BatchNorm
+        # runs inside bn2's kernels (_dual_downsample); needs the gate bits
+        self.dual_bn = dual_bn and gate_bits and fused
         self.conv1 = conv3x3(cin, planes, stride)
         self.conv2 = conv3x3(planes, planes)
         self.downsample = downsample
@@ -78,12 +118,10 @@ class BasicBlock(nn.Module):
 
     def forward(self, x):
         x, skip = _split(x)
-        identity = (self.downsample(skip) if self.downsample is not None
-                    else skip)
+        identity, x_d = _skip_path(self, skip)
         if self.fused:
             out = self.bn1(self.conv1(x))
-            return _last_bn(self.bn2, self.conv2(out), identity,
-                            getattr(self, "fork", False))
+            return _close(self, self.bn2, self.conv2(out), identity, x_d)
         out = self.relu(self.bn1(self.conv1(x)))
         out = self.bn2(self.conv2(out))
         return self.relu(out + identity)
@@ -93,10 +131,11 @@ class Bottleneck(nn.Module):
     expansion = 4
 
     def __init__(self, cin, planes, stride=1, downsample=None, fused=False,
-                 fork=False, gate_bits=True):
+                 fork=False, gate_bits=True, dual_bn=True):
         super().__init__()
         self.fused = fused
         self.fork = fork and fused  # as in BasicBlock
+        self.dual_bn = dual_bn and gate_bits and fused  # as in BasicBlock
         self.conv1 = conv1x1(cin, planes)
         self.conv2 = conv3x3(planes, planes, stride)
         self.conv3 = conv1x1(planes, planes * self.expansion)
@@ -114,13 +153,11 @@ class Bottleneck(nn.Module):
 
     def forward(self, x):
         x, skip = _split(x)
-        identity = (self.downsample(skip) if self.downsample is not None
-                    else skip)
+        identity, x_d = _skip_path(self, skip)
         if self.fused:
             out = self.bn1(self.conv1(x))
             out = self.bn2(self.conv2(out))
-            return _last_bn(self.bn3, self.conv3(out), identity,
-                            getattr(self, "fork", False))
+            return _close(self, self.bn3, self.conv3(out), identity, x_d)
         out = self.relu(self.bn1(self.conv1(x)))
         out = self.relu(self.bn2(self.conv2(out)))
         out = self.bn3(self.conv3(out))
@@ -137,9 +174,15 @@ class ResNet(nn.Module):
         fused: bool = False,
         fork_grads: bool = True,
         gate_bits: bool = True,
+        dual_bn: bool = True,
     ):
         super().__init__()
         self.fused = fused
+        # fused models with gate bits: the first block of a stage runs its
+        # downsample BatchNorm inside the closing BN's kernels (dual BN,
+        # msbn/nn/fused.py bn_add_bn_act).  Same math either way; False
+        # keeps the two layers apart.
+        self.dual_bn = dual_bn and gate_bits and fused
         # fused models: each block's closing BN keeps its activation gate as
         # one bit per element instead of re-reading the residual in backward.
         # Same math either way; False keeps the recomputing route.
@@ -182,7 +225,7 @@ class ResNet(nn.Module):
             )
         layers = [block(self.inplanes, planes, stride, downsample,
                         fused=self.fused, fork=fork[0],
-                        gate_bits=self.gate_bits)]
+                        gate_bits=self.gate_bits, dual_bn=self.dual_bn)]
         self.inplanes = planes * block.expansion
         for i in range(1, blocks):
             layers.append(block(self.inplanes, planes, fused=self.fused,
@@ -223,12 +266,16 @@ class ResNet(nn.Module):
 
 
 def resnet18(num_classes: int = 1000, fused: bool = False,
-             fork_grads: bool = True, gate_bits: bool = True) -> ResNet:
+             fork_grads: bool = True, gate_bits: bool = True,
+             dual_bn: bool = True) -> ResNet:
     return ResNet(BasicBlock, [2, 2, 2, 2], num_classes, fused=fused,
-                  fork_grads=fork_grads, gate_bits=gate_bits)
+                  fork_grads=fork_grads, gate_bits=gate_bits,
+                  dual_bn=dual_bn)
 
 
 def resnet50(num_classes: int = 1000, fused: bool = False,
-             fork_grads: bool = True, gate_bits: bool = True) -> ResNet:
+             fork_grads: bool = True, gate_bits: bool = True,
+             dual_bn: bool = True) -> ResNet:
     return ResNet(Bottleneck, [3, 4, 6, 3], num_classes, fused=fused,
-                  fork_grads=fork_grads, gate_bits=gate_bits)
+                  fork_grads=fork_grads, gate_bits=gate_bits,
+                  dual_bn=dual_bn)

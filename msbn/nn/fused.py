@@ -476,6 +476,330 @@ def bn_act_maxpool(bn, pool, input: torch.Tensor, fork: bool = False):
     )
 
 
+def _combined4(parts, C: int):
+    """The dual reduce returns its four sums as views of ONE contiguous
+    ``[4C]`` buffer: all_reduce that buffer itself.  Anything else (the
+    single ops' two ``[2C]`` buffers, CPU) is cat-copied."""
+    first = parts[0]
+    adjacent = all(
+        p.is_contiguous() and p.numel() == C
+        and p.untyped_storage().data_ptr() == first.untyped_storage().data_ptr()
+        and p.data_ptr() == first.data_ptr() + i * C * first.element_size()
+        for i, p in enumerate(parts)
+    )
+    if adjacent:
+        base = first.new_empty(0)
+        base.set_(first.untyped_storage(), first.storage_offset(), (4 * C,),
+                  (1,))
+        return base
+    return torch.cat(parts)
+
+
+class SyncBatchNormDualActFunction(torch.autograd.Function):
+    """``relu(bn(x) + bn_skip(x_skip))`` as one layer: the first block of a
+    ResNet stage, whose skip path has a BatchNorm of its own
+    (docs/KERNEL_DESIGN.md "Dual BN").
+
+    On the dual kernels the skip BN's output is never stored, the backward
+    reads the gated gradient once per pass for both layers, and the saved
+    tensors are x, x_skip, the gate bits and per-channel vectors.  Results
+    are bit-identical to ``bn(x, residual=bn_skip(x_skip), fork=fork)``.
+
+    The function fixes the collective schedule, whatever kernels run on this
+    rank: forward statistics of the skip layer, then of the main layer;
+    backward ONE all_reduce of ``[sum_dy | sum_dy_xmu | sum_dy_2 |
+    sum_dy_xmu_2]`` (4C fp32).  The composition issues the same collectives
+    in another order, so every rank of a group must be on the same route:
+    callers choose it from properties that are equal on all ranks
+    (``bn_add_bn_act``).  Whether the dual KERNELS run is decided here, per
+    rank: an empty input, tensors that are not dense channels-last bf16 /
+    half with C a multiple of 8 and 16-byte aligned, or a skip input that
+    needs no gradient run the single-BN ops instead and pack their sums into
+    the same message (CPU tensors included)."""
+
+    @staticmethod
+    def forward(ctx, input, input2, weight, bias, weight2, bias2,
+                running_mean, running_var, running_mean2, running_var2,
+                eps: float, eps2: float, momentum: float, momentum2: float,
+                process_group, world_size: int, fork: bool = False):
+        x = _contig(input)
+        x2 = _contig(input2)
+        weight, bias, weight2, bias2 = (
+            None if t is None else t.contiguous()
+            for t in (weight, bias, weight2, bias2)
+        )
+        use_sync = world_size > 1 or (
+            process_group is not None and _force_sync()
+        )
+        mean2, invstd2, count2, coefs2 = compute_sync_stats(
+            x2, eps2, momentum2, running_mean2, running_var2,
+            process_group, world_size, weight2, bias2, want_coefs=True,
+        )
+        # x and x_skip have one shape on every rank, so the skip layer's
+        # total count is the main layer's: one copy is kept, and this one is
+        # released before anything else is allocated
+        del count2
+        mean, invstd, count, coefs = compute_sync_stats(
+            x, eps, momentum, running_mean, running_var,
+            process_group, world_size, weight, bias, want_coefs=True,
+        )
+        # what the composition's residual, bn_skip(x_skip), would require
+        need_r = any(ctx.needs_input_grad[i] for i in (1, 4, 5))
+        y = r = gate = None
+        dual = False
+        if x.numel() == 0:
+            y = torch.empty_like(x)
+        elif (x.is_cuda and ctx.needs_input_grad[1] and coefs is not None
+                and coefs2 is not None and x2.stride() == x.stride()):
+            bits = ops.gate_bits_empty(x)
+            y, dual = ops.batch_norm_elemt_act_dual(
+                x, x2, coefs, coefs2, True, 0.0, bits
+            )
+            if dual:
+                gate = bits
+        if y is None:
+            # the composition's own two launches
+            r = _match_layout(ops.batch_norm_elemt_act(
+                x2, None, weight2, bias2, mean2, invstd2, False, coefs2), x)
+            if need_r and x.is_cuda:
+                y, gate = ops.batch_norm_elemt_act(
+                    x, r, weight, bias, mean, invstd, True, coefs, 0.0,
+                    ops.gate_bits_empty(x),
+                )
+            else:
+                y = ops.batch_norm_elemt_act(
+                    x, r, weight, bias, mean, invstd, True, coefs, 0.0
+                )
+            if gate is not None:
+                r = None
+        ctx.dual = dual
+        ctx.need_r = need_r
+        ctx.use_sync = use_sync
+        ctx.process_group = process_group
+        # Per-channel vectors: those of the composition's two layers, with
+        # the skip layer's [scale | shift] in the place of its count on the
+        # dual route.  The forward kernel reads that vector while y exists,
+        # so releasing it afterwards could not lower the peak; keeping it
+        # means that nothing is alive during the forward that is not held
+        # after it, and the layer holds what the composition holds.
+        ctx.save_for_backward(x, x2, r, gate, weight, bias, weight2, bias2,
+                              mean, invstd, mean2, invstd2, count, coefs,
+                              coefs2 if dual else None)
+        if not fork:
+            return y
+        # an unused output then arrives as None, not as a full-size zero fill
+        ctx.set_materialize_grads(False)
+        return y, y.detach()
+
+    @staticmethod
+    def backward(ctx, grad_output, grad_skip=None):
+        if grad_output is None:  # fork with only the second output used
+            grad_output, grad_skip = grad_skip, None
+        if grad_output is None:
+            return (None,) * 17
+        (x, x2, r, gate, weight, bias, weight2, bias2, mean, invstd, mean2,
+         invstd2, count, coefs, _coefs2) = ctx.saved_tensors
+        need_x, need_x2 = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        need_w = weight is not None and ctx.needs_input_grad[2]
+        need_b = bias is not None and ctx.needs_input_grad[3]
+        need_w2 = weight2 is not None and ctx.needs_input_grad[4]
+        need_b2 = bias2 is not None and ctx.needs_input_grad[5]
+        need_r = ctx.need_r
+        process_group = ctx.process_group
+        sync = ctx.use_sync and (need_x or need_r)
+        C = int(x.shape[1])
+
+        def all_reduce(combined):
+            from msbn.utils import debug as _dbg
+            if _dbg.enabled():  # peers verify; skipping would hang them
+                _dbg.verify_collective("syncbn.bwd.all_reduce", combined,
+                                       process_group)
+            dist.all_reduce(combined, dist.ReduceOp.SUM, group=process_group)
+            from msbn.utils.logging import comm_log
+            comm_log.record("all_reduce", combined.numel() * 4,
+                            f"syncbn bwd dual C={C}")
+
+        def result(dx, dx2, gw, gb, gw2, gb2):
+            return (
+                dx if need_x else None, dx2 if need_x2 else None,
+                gw if need_w else None, gb if need_b else None,
+                gw2 if need_w2 else None, gb2 if need_b2 else None,
+            ) + (None,) * 11
+
+        # both gradients of a forked output reach the GPU reduce unsummed
+        fold = grad_skip is not None and x.is_cuda and x.numel() > 0
+        if grad_skip is not None and not fold:
+            grad_output = grad_output + grad_skip
+            grad_skip = None
+        grad_output = _match_layout(grad_output, x)
+        if fold:
+            grad_skip = _match_layout(grad_skip, x)
+
+        if x.numel() == 0:
+            # empty-input rank (join): contribute zeros, keep peers unblocked
+            if sync:
+                all_reduce(torch.zeros(4 * C, dtype=torch.float32,
+                                       device=grad_output.device))
+            return result(
+                torch.empty_like(grad_output), torch.empty_like(x2),
+                None if weight is None else torch.zeros_like(weight),
+                None if bias is None else torch.zeros_like(bias),
+                None if weight2 is None else torch.zeros_like(weight2),
+                None if bias2 is None else torch.zeros_like(bias2),
+            )
+
+        if ctx.dual:
+            gm = torch.empty_like(grad_output)
+            (sum_dy, sum_dy_xmu, gw, gb, sum_dy2, sum_dy_xmu2, gw2, gb2) = (
+                ops.batch_norm_backward_reduce_act(
+                    grad_output, x, None, mean, invstd, weight, bias, True,
+                    need_x, need_w, need_b, coefs, gm, 0.0, grad_skip,
+                    gate=gate, dual=(x2, mean2, invstd2, weight2),
+                )
+            )
+            combined = _combined4(
+                (sum_dy, sum_dy_xmu, sum_dy2, sum_dy_xmu2), C)
+            if sync:
+                all_reduce(combined)
+            if need_x:
+                dx, dx2 = ops.batch_norm_backward_elemt_dual(
+                    gm, x, x2, mean, mean2, invstd, invstd2, weight, weight2,
+                    combined, count,
+                )
+            else:
+                dx = None
+                dx2 = ops.batch_norm_backward_elemt(
+                    gm, x2, mean2, invstd2, weight2, combined[2 * C:3 * C],
+                    combined[3 * C:], count,
+                )
+            return result(dx, dx2, gw, gb, gw2, gb2)
+
+        # the single-BN ops of the composition, their sums in one message
+        use_gm = fold or need_r
+        gm = torch.empty_like(grad_output) if use_gm else None
+        sum_dy, sum_dy_xmu, gw, gb = ops.batch_norm_backward_reduce_act(
+            grad_output, x, r, mean, invstd, weight, bias, True, need_x,
+            need_w, need_b, coefs, gm, 0.0, grad_skip,
+            **({} if gate is None else {"gate": gate}),
+        )
+        gw2 = gb2 = g2 = None
+        if need_r:
+            g2 = _match_layout(gm, x2)
+            sum_dy2, sum_dy_xmu2, gw2, gb2 = ops.batch_norm_backward_reduce(
+                g2, x2, mean2, invstd2, weight2, need_x2, need_w2, need_b2,
+            )
+        else:
+            sum_dy2 = sum_dy_xmu2 = None
+        # a layer whose input needs no gradient sends zeros (the CPU ops
+        # then form no sums at all)
+        zeros = torch.zeros(C, dtype=torch.float32, device=x.device)
+        combined = torch.cat([
+            zeros if s is None else s
+            for s in (sum_dy, sum_dy_xmu, sum_dy2, sum_dy_xmu2)
+        ])
+        if sync:
+            all_reduce(combined)
+        dx = dx2 = None
+        if need_x:
+            if use_gm:
+                dx, _ = ops.batch_norm_backward_elemt_act(
+                    gm, x, None, mean, invstd, weight, bias, combined[:C],
+                    combined[C:2 * C], count, False, False, coefs,
+                )
+            else:
+                dx, _ = ops.batch_norm_backward_elemt_act(
+                    grad_output, x, r, mean, invstd, weight, bias,
+                    combined[:C], combined[C:2 * C], count, True, False,
+                    coefs, 0.0,
+                )
+        if need_x2:
+            dx2 = ops.batch_norm_backward_elemt(
+                g2, x2, mean2, invstd2, weight2, combined[2 * C:3 * C],
+                combined[3 * C:], count,
+            )
+        return result(dx, dx2, gw, gb, gw2, gb2)
+
+
+def _hooked(m) -> bool:
+    return bool(m._forward_hooks or m._forward_pre_hooks
+                or m._backward_hooks or m._backward_pre_hooks)
+
+
+def dual_bn_eligible(bn, bn_skip, x: torch.Tensor) -> bool:
+    """True when ``bn(x, residual=bn_skip(x_skip))`` runs as
+    SyncBatchNormDualActFunction.  The two routes issue their collectives in
+    different orders, so this looks only at what is equal on every rank of a
+    group by construction: the module types and flags (a training-mode
+    out-of-place relu SyncBatchNormAct2d with gate bits, a training-mode
+    SyncBatchNorm proper, no hooks, equal ``num_features`` and process
+    group), and a 4-D bf16 / half input on a CUDA device.  Sizes, strides
+    and addresses are the function's own business."""
+    if not (
+        type(bn) is SyncBatchNormAct2d and type(bn_skip) is SyncBatchNorm
+        and bn.training and bn_skip.training
+        and bn.relu and getattr(bn, "negative_slope", 0.0) == 0.0
+        and getattr(bn, "gate_bits", False)
+        and not getattr(bn, "inplace", False)
+        and not _hooked(bn) and not _hooked(bn_skip)
+        and bn.num_features == bn_skip.num_features
+        and bn.process_group is bn_skip.process_group
+        and x.is_cuda and x.dim() == 4
+        and x.dtype in (torch.bfloat16, torch.float16)
+    ):
+        return False
+    return True
+
+
+def bn_add_bn_act(bn, bn_skip, x: torch.Tensor, x_skip: torch.Tensor,
+                  fork: bool = False):
+    """``bn(x, residual=bn_skip(x_skip), fork=fork)`` for the closing
+    SyncBatchNormAct2d ``bn`` of a residual block and the SyncBatchNorm
+    ``bn_skip`` of its downsample path: one dual layer where
+    ``dual_bn_eligible``, exactly that composition otherwise (frozen or
+    swapped modules, eval mode, fp32, CPU, hooks).  ``fork=True`` returns a
+    ``(main, skip)`` pair (SyncBatchNormAct2d.forward).  Both modules'
+    running statistics and ``num_batches_tracked`` move as their own
+    ``forward`` would move them."""
+    eligible = dual_bn_eligible(bn, bn_skip, x)
+    process_group = None
+    world_size = 1
+    if eligible and dist.is_available() and dist.is_initialized():
+        process_group = bn.process_group or dist.group.WORLD
+        world_size = dist.get_world_size(process_group)
+    if eligible and not (world_size > 1 or (
+            process_group is not None and _force_sync())):
+        # no collectives, so nothing to keep in step: small NCHW planes
+        # stay on the composition's single-launch kernels
+        eligible = not (
+            ops.bn_fused_local_eligible(x, bn.weight, bn.bias,
+                                        bn.running_mean, bn.running_var)
+            or ops.bn_fused_local_eligible(x_skip, bn_skip.weight,
+                                           bn_skip.bias, bn_skip.running_mean,
+                                           bn_skip.running_var)
+        )
+    if not eligible:
+        if fork:
+            return bn(x, residual=bn_skip(x_skip), fork=True)
+        return bn(x, residual=bn_skip(x_skip))
+    for m, t in ((bn_skip, x_skip), (bn, x)):
+        m._check_input_dim(t)
+        m._check_non_zero_input_channels(t)
+        if m.track_running_stats and m.num_batches_tracked is not None:
+            m.num_batches_tracked.add_(1)
+
+    def running(m):
+        if m.track_running_stats:
+            return m.running_mean, m.running_var
+        return None, None
+
+    return SyncBatchNormDualActFunction.apply(
+        x, x_skip, bn.weight, bn.bias, bn_skip.weight, bn_skip.bias,
+        *running(bn), *running(bn_skip), bn.eps, bn_skip.eps,
+        _momentum_factor(bn), _momentum_factor(bn_skip), process_group,
+        world_size, fork,
+    )
+
+
 class InPlaceSyncBatchNormActFunction(torch.autograd.Function):
     """In-Place Activated SyncBatchNorm (Rota Bulo et al., 2018): the output
     ``y = act(bn(x))`` is written over ``x`` and the backward works from ``y``

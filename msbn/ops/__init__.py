@@ -250,7 +250,7 @@ def batch_norm_backward_reduce_act(grad_out, input, residual, mean, invstd,
                                    weight, bias, relu_mask, input_g, weight_g,
                                    bias_g, coefs=None, gm_out=None,
                                    negative_slope: float = 0.0,
-                                   grad_out2=None, gate=None):
+                                   grad_out2=None, gate=None, *, dual=None):
     """First pass of the fused BN backward.  ``grad_out2`` is the second
     gradient of a forked output, delivered unsummed: the incoming gradient is
     ``grad_out + grad_out2`` rounded to the input dtype once (the tensor an
@@ -260,7 +260,41 @@ def batch_norm_backward_reduce_act(grad_out, input, residual, mean, invstd,
     ``gate``: the bits ``batch_norm_elemt_act(gate_out=)`` returned for this
     layer, passed INSTEAD of ``residual`` (which must be None): the kernel
     takes the activation's branch from them.  GPU only; requires
-    ``relu_mask`` and ``gm_out``.  Same results as with the residual."""
+    ``relu_mask`` and ``gm_out``.  Same results as with the residual.
+
+    ``dual=(input2, mean2, invstd2, weight2)`` (keyword only; dual BN,
+    docs/KERNEL_DESIGN.md): the layer's residual was a second BatchNorm's
+    output, ``bn2(input2)``, and the same kernel also forms that layer's
+    sums over the gated gradient it writes to ``gm_out``.  Needs ``gate``,
+    ``relu_mask`` with a zero slope and ``gm_out``; GPU only.  The call then
+    returns ``(sum_dy, sum_dy_xmu, grad_weight, grad_bias, sum_dy_2,
+    sum_dy_xmu_2, grad_weight_2, grad_bias_2)``, the four sums being views
+    into ONE contiguous fp32 ``[4C]`` buffer in that order (one all_reduce
+    for the pair).  ``weight_g`` / ``bias_g`` are the main layer's; the skip
+    layer's affine gradients are formed whenever it has a weight (they are
+    [C] vectors).  Inputs the dual kernel declines (a
+    gradient off 16-byte alignment, ...) run the two single reduces; same
+    results."""
+    if dual is not None:
+        if not input.is_cuda:
+            raise ValueError("the dual reduce exists on the GPU path only")
+        if (gate is None or residual is not None or gm_out is None
+                or not relu_mask or negative_slope != 0.0):
+            raise ValueError(
+                "dual needs gate, gm_out, relu_mask with a zero slope and no "
+                "residual"
+            )
+        input2, mean2, invstd2, weight2 = dual
+        sums, gw, gb, gw2, gb2 = (
+            _require_hip().batch_norm_backward_reduce_act_dual(
+                grad_out, input, input2, mean, mean2, invstd, invstd2,
+                weight, weight2, weight_g, bias_g, weight2 is not None,
+                weight2 is not None, gm_out, grad_out2, gate,
+            )
+        )
+        C = input.shape[1]
+        return (sums[:C], sums[C:2 * C], gw, gb, sums[2 * C:3 * C],
+                sums[3 * C:], gw2, gb2)
     if input.is_cuda:
         return _require_hip().batch_norm_backward_reduce_act(
             grad_out, input, residual, mean, invstd, weight, bias, relu_mask,
@@ -289,6 +323,40 @@ def batch_norm_backward_elemt_act(grad_out, input, residual, mean, invstd,
     return _ref.batch_norm_backward_elemt_act(
         grad_out, input, residual, mean, invstd, weight, bias, sum_dy,
         sum_dy_xmu, count, relu_mask, want_res_grad, negative_slope,
+    )
+
+
+def batch_norm_elemt_act_dual(input, input2, coefs, coefs2, relu: bool,
+                              negative_slope: float, gate_out):
+    """``relu(bn(input) + bn2(input2))`` in one kernel (dual BN,
+    docs/KERNEL_DESIGN.md): ``coefs`` / ``coefs2`` are the two layers' packed
+    ``[scale | shift]`` (``bn_make_coefs``) and ``gate_out``
+    (``gate_bits_empty(input)``) receives the gate bits.  ``bn2``'s output is
+    rounded to the input dtype in registers and never stored, so ``y`` and
+    the bits are those of ``batch_norm_elemt`` followed by
+    ``batch_norm_elemt_act(residual=, gate_out=)``.
+
+    Returns ``(y, stored)``.  ``stored`` is False, ``y`` None and nothing is
+    written when the kernel declines: anything but dense channels-last 4-D
+    bf16 / half GPU tensors with C a multiple of 8 and 16-byte aligned
+    pointers, and any activation but plain ReLU."""
+    if not input.is_cuda:
+        return None, False
+    y, stored = _require_hip().batch_norm_elemt_act_dual(
+        input, input2, coefs, coefs2, relu, negative_slope, gate_out
+    )
+    return (y if stored else None), stored
+
+
+def batch_norm_backward_elemt_dual(gm, input, input2, mean, mean2, invstd,
+                                   invstd2, weight, weight2, sums, count):
+    """Second backward pass of a dual BN pair: ``(dx, dx2)`` from one read of
+    ``gm``.  ``sums`` is the ``[4C]`` buffer the dual reduce returned (after
+    its all_reduce).  Same bits as two ``batch_norm_backward_elemt`` calls.
+    Takes what ``batch_norm_elemt_act_dual`` takes and raises otherwise."""
+    return _require_hip().batch_norm_backward_elemt_dual(
+        gm, input, input2, mean, mean2, invstd, invstd2, weight, weight2,
+        sums, count,
     )
 
 
@@ -456,7 +524,13 @@ def launch_plan(kind: str, input: torch.Tensor, others=(), coefs=None) -> dict:
       ``"bwd_reduce_pool"``   input = x, others = (grad_out, grad_out2, codes)
       ``"bwd_elemt_pool"``    input = x, others = (grad_out, grad_out2,
                                                    codes), coefs
-    ``None`` entries of ``others`` are absent tensors.
+      ``"elemt_dual"``        input = x, others = (x2[, coefs2]), coefs
+      ``"bwd_reduce_dual"``   input = x, others = (grad_out, x2, gm_out,
+                                                   grad_out2, gate)
+      ``"bwd_elemt_dual"``    input = x, others = (gm, x2)
+    ``None`` entries of ``others`` are absent tensors.  The dual kinds
+    report path ``"nhwc"`` with their single counterparts' numbers plus
+    ``dual: True``, or ``"ineligible"`` where the dual kernels decline.
 
     Returns a dict with ``path`` (``"nchw_vec"``, ``"nchw_flat"``, ``"nhwc"``,
     ``"small_plane"``, or ``"ineligible"`` for ``fused_local``), ``V`` and
@@ -469,7 +543,7 @@ def launch_plan(kind: str, input: torch.Tensor, others=(), coefs=None) -> dict:
     path, numbers = _require_hip().launch_plan(kind, input, list(others), coefs)
     plan = dict(numbers)
     plan["path"] = path
-    for flag in ("multi_trip", "gate"):
+    for flag in ("multi_trip", "gate", "dual"):
         if flag in plan:
             plan[flag] = bool(plan[flag])
     return plan
@@ -481,6 +555,8 @@ __all__ = [
     "gate_bits_empty",
     "bn_frozen_coefs",
     "batch_norm_frozen_backward_elemt",
+    "batch_norm_elemt_act_dual",
+    "batch_norm_backward_elemt_dual",
     "batch_norm_elemt_act_pool",
     "batch_norm_backward_reduce_act_pool",
     "batch_norm_backward_elemt_act_pool",

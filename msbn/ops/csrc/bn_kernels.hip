@@ -957,6 +957,230 @@ __global__ void bn_bwd_elemt_nhwc(const T* __restrict__ dy,
 }
 
 // =====================================================================
+// dual BN: relu(bn(x) + bn_d(x_d)), the first block of a ResNet stage, whose
+// skip path has a BatchNorm of its own (docs/KERNEL_DESIGN.md "Dual BN").
+// Three kernels stand in for the five of the composition
+//   bn_elemt_nhwc<none>(x_d) -> r,  bn_elemt_nhwc<relu, RES, GATE>(x, r)
+//   bn_bwd_reduce_partial_nhwc<relu, GM, DY2?, GATE>, then <none> on (gm, x_d)
+//   bn_bwd_elemt_nhwc<none> on (gm, x) and on (gm, x_d)
+// so r is never stored and gm is read once per pass for both layers.
+// Channels-last, 8 elements per thread, bf16 / half, ReLU, gate bits; the
+// host declines everything else and the composition runs.  Every expression
+// is the one the single kernels use, in their order, and the reduce runs on
+// the single reduce's launch plan: the results are the composition's bits.
+// =====================================================================
+template <typename T>
+__global__ void bn_elemt_dual_nhwc(const T* __restrict__ x,
+                                   const T* __restrict__ x2,
+                                   T* __restrict__ y,
+                                   const float* __restrict__ scale,
+                                   const float* __restrict__ shift,
+                                   const float* __restrict__ scale2,
+                                   const float* __restrict__ shift2,
+                                   int64_t total, int64_t C,
+                                   unsigned char* __restrict__ gate_out) {
+  constexpr int V = 8;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+       i * V < total; i += stride) {
+    const int64_t e = i * V;
+    const int64_t c = e % C;
+    Pack<T, V> px = nt_load<T, V>(&x[e]);
+    Pack<T, V> px2 = nt_load<T, V>(&x2[e]);
+    Pack<float, V> ps = *reinterpret_cast<const Pack<float, V>*>(&scale[c]);
+    Pack<float, V> pb = *reinterpret_cast<const Pack<float, V>*>(&shift[c]);
+    Pack<float, V> ps2 = *reinterpret_cast<const Pack<float, V>*>(&scale2[c]);
+    Pack<float, V> pb2 = *reinterpret_cast<const Pack<float, V>*>(&shift2[c]);
+    Pack<T, V> py;
+    unsigned bits = 0;
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+      // the skip BN's output, rounded to T as its own kernel stores it
+      const T r = from_f<T>(to_f(px2.v[k]) * ps2.v[k] + pb2.v[k]);
+      float z = to_f(px.v[k]) * ps.v[k] + pb.v[k];
+      z += to_f(r);
+      bits |= (unsigned)act_pass<kActRelu>(z) << k;
+      z = act_fwd<kActRelu>(z, 0.f);
+      py.v[k] = from_f<T>(z);
+    }
+    nt_store<T, V>(&y[e], py);
+    gate_store(gate_out, e, bits);
+  }
+}
+
+// Block tree reduction of one layer's per-thread fp64 pairs over sdata and
+// the store of the block's partials (the tail of bn_bwd_reduce_partial_nhwc).
+template <int V>
+__device__ __forceinline__ void nhwc_tree_reduce_store(
+    const double (&a)[V], const double (&b)[V], double* sdata,
+    double* __restrict__ ws, int64_t c, int64_t C, int lpr, int rpi,
+    int rowoff, bool active) {
+#pragma unroll
+  for (int k = 0; k < V; ++k) {
+    sdata[k * MSBN_BLOCK + threadIdx.x] = a[k];
+    sdata[(V + k) * MSBN_BLOCK + threadIdx.x] = b[k];
+  }
+  for (int st = 1; st < rpi; st <<= 1) {
+    __syncthreads();
+    if (active && (rowoff & ((st << 1) - 1)) == 0 && rowoff + st < rpi) {
+      const int other = threadIdx.x + st * lpr;
+#pragma unroll
+      for (int k = 0; k < V; ++k) {
+        sdata[k * MSBN_BLOCK + threadIdx.x] += sdata[k * MSBN_BLOCK + other];
+        sdata[(V + k) * MSBN_BLOCK + threadIdx.x] +=
+            sdata[(V + k) * MSBN_BLOCK + other];
+      }
+    }
+  }
+  __syncthreads();
+  if (rowoff == 0 && c < C) {
+    const int64_t chunk = blockIdx.y;
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+      if (c + k < C) {
+        double* out = ws + ((c + k) * gridDim.y + chunk) * 2;
+        out[0] = sdata[k * MSBN_BLOCK + threadIdx.x];
+        out[1] = sdata[(V + k) * MSBN_BLOCK + threadIdx.x];
+      }
+    }
+  }
+}
+
+// g*(x - mean) rounded on its own, never fused into the add that follows:
+// what the single V = 8 reduce kernels compile to, for both layers.  The
+// compiler is otherwise free to contract each kernel differently (it fused
+// the skip layer's product here and not in the single kernel), and one fused
+// product moves the last bit of a sum.
+__device__ __forceinline__ float mul_unfused(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
+// Traversal, gate and flush interval of
+// bn_bwd_reduce_partial_nhwc<T, 8, relu, false, true, DY2, true>.  The gated
+// gradient g is a value of T (the relu gate passes or zeroes one), so the
+// skip layer's plain reduce over gm would add the very g in the very order:
+// its sum of g IS this layer's, and only sum g*(x_d - mean_d) needs
+// accumulators of its own.  The two layers' pairs go through the tree one
+// after the other over the same 32 KiB of LDS.
+template <typename T, bool DY2>
+__global__ void bn_bwd_reduce_dual_partial_nhwc(
+    const T* __restrict__ dy, const T* __restrict__ dy2,
+    const T* __restrict__ x, const T* __restrict__ x2,
+    T* __restrict__ gm_out, const float* __restrict__ mean,
+    const float* __restrict__ mean2, double* __restrict__ ws,
+    double* __restrict__ ws2, int64_t rows, int64_t C, int64_t chunk_rows,
+    int lpr, const unsigned char* __restrict__ gate) {
+  constexpr int V = 8;
+  const int rpi = blockDim.x / lpr;
+  const int lane = threadIdx.x % lpr;
+  const int rowoff = threadIdx.x / lpr;
+  const bool active = rowoff < rpi;
+  const int64_t c = (int64_t)blockIdx.x * lpr * V + (int64_t)lane * V;
+  const bool inb = active && (c + V <= C);
+
+  // acc2: only its second component is read; the first is this layer's
+  AccPair acc[V], acc2[V];
+  float m[V], m2[V];
+#pragma unroll
+  for (int k = 0; k < V; ++k) m[k] = m2[k] = 0.f;
+  if (inb) {
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+      m[k] = mean[c + k];
+      m2[k] = mean2[c + k];
+    }
+    const int64_t r0 = (int64_t)blockIdx.y * chunk_rows;
+    const int64_t r1 = i64min(r0 + chunk_rows, rows);
+    int since_flush = 0;
+    for (int64_t r = r0 + rowoff; r < r1; r += rpi) {
+      Pack<T, V> pg = nt_load<T, V>(&dy[r * C + c]);
+      Pack<T, V> px = nt_load<T, V>(&x[r * C + c]);
+      Pack<T, V> px2 = nt_load<T, V>(&x2[r * C + c]);
+      Pack<T, V> pg2, pm;
+      if (DY2) pg2 = nt_load<T, V>(&dy2[r * C + c]);
+      const unsigned bits = gate_load(gate, r * C + c);
+#pragma unroll
+      for (int k = 0; k < V; ++k) {
+        float g = DY2 ? fork_grad(pg.v[k], pg2.v[k]) : to_f(pg.v[k]);
+        const float xv = to_f(px.v[k]);
+        const float xv2 = to_f(px2.v[k]);
+        g = act_gate_bit<kActRelu>((bits >> k) & 1u, g, 0.f);
+        pm.v[k] = from_f<T>(g);
+        acc[k].add2(g, mul_unfused(g, xv - m[k]));
+        acc2[k].add2(g, mul_unfused(g, xv2 - m2[k]));
+      }
+      nt_store<T, V>(&gm_out[r * C + c], pm);
+      if (++since_flush == MSBN_ACC_FLUSH) {
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+          acc[k].flush();
+          acc2[k].flush();
+        }
+        since_flush = 0;
+      }
+    }
+  }
+  double a[V], b[V], b2[V];
+#pragma unroll
+  for (int k = 0; k < V; ++k) {
+    acc[k].flush();
+    acc2[k].flush();
+    a[k] = acc[k].a;
+    b[k] = acc[k].b;
+    b2[k] = acc2[k].b;
+  }
+  // [k][tid] planes as in bn_bwd_reduce_partial_nhwc (conflict-free)
+  __shared__ double sdata[MSBN_BLOCK * V * 2];
+  nhwc_tree_reduce_store<V>(a, b, sdata, ws, c, C, lpr, rpi, rowoff, active);
+  __syncthreads();
+  nhwc_tree_reduce_store<V>(a, b2, sdata, ws2, c, C, lpr, rpi, rowoff, active);
+}
+
+// dx = a*gm + b*x + d and dx2 = a2*gm + b2*x2 + d2 from one read of gm: the
+// expressions of bn_bwd_elemt_nhwc<T, 8, none, false, false>.  co / co2 are
+// the packed [a | b | d] rows bn_affine_bwd wrote.
+template <typename T>
+__global__ void bn_bwd_elemt_dual_nhwc(const T* __restrict__ gm,
+                                       const T* __restrict__ x,
+                                       const T* __restrict__ x2,
+                                       T* __restrict__ dx,
+                                       T* __restrict__ dx2,
+                                       const float* __restrict__ co,
+                                       const float* __restrict__ co2,
+                                       int64_t total, int64_t C) {
+  constexpr int V = 8;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+       i * V < total; i += stride) {
+    const int64_t e = i * V;
+    const int64_t c = e % C;
+    Pack<T, V> pg = nt_load<T, V>(&gm[e]);
+    Pack<T, V> px = nt_load<T, V>(&x[e]);
+    Pack<T, V> px2 = nt_load<T, V>(&x2[e]);
+    Pack<float, V> pa = *reinterpret_cast<const Pack<float, V>*>(&co[c]);
+    Pack<float, V> pb = *reinterpret_cast<const Pack<float, V>*>(&co[C + c]);
+    Pack<float, V> pd =
+        *reinterpret_cast<const Pack<float, V>*>(&co[2 * C + c]);
+    Pack<float, V> pa2 = *reinterpret_cast<const Pack<float, V>*>(&co2[c]);
+    Pack<float, V> pb2 = *reinterpret_cast<const Pack<float, V>*>(&co2[C + c]);
+    Pack<float, V> pd2 =
+        *reinterpret_cast<const Pack<float, V>*>(&co2[2 * C + c]);
+    Pack<T, V> po, po2;
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+      const float g = to_f(pg.v[k]);
+      const float xv = to_f(px.v[k]);
+      const float xv2 = to_f(px2.v[k]);
+      po.v[k] = from_f<T>(pa.v[k] * g + pb.v[k] * xv + pd.v[k]);
+      po2.v[k] = from_f<T>(pa2.v[k] * g + pb2.v[k] * xv2 + pd2.v[k]);
+    }
+    nt_store<T, V>(&dx[e], po);
+    nt_store<T, V>(&dx2[e], po2);
+  }
+}
+
+// =====================================================================
 // frozen path: the statistics are the (fixed) running stats, so there is no
 // batch reduction anywhere.  One tiny kernel folds (running_mean,
 // running_var, eps, weight, bias) into the packed [scale | shift] buffer the
@@ -3853,6 +4077,255 @@ batch_norm_bwd_fused_local(const at::Tensor& grad_out, const at::Tensor& input,
 }
 
 // ---------------------------------------------------------------------------
+// dual BN: relu(bn(x) + bn_d(x_d)) (kernels: "dual BN" above)
+// ---------------------------------------------------------------------------
+namespace {
+// the dual kernels exist for the two 2-byte dtypes only
+#define MSBN_DISPATCH_HALF_TYPES(TYPE, NAME, ...)                           \
+  [&] {                                                                     \
+    switch (TYPE) {                                                         \
+      case at::kBFloat16: {                                                 \
+        using native_t = __hip_bfloat16;                                    \
+        return __VA_ARGS__();                                               \
+      }                                                                     \
+      case at::kHalf: {                                                     \
+        using native_t = __half;                                            \
+        return __VA_ARGS__();                                               \
+      }                                                                     \
+      default:                                                              \
+        TORCH_CHECK(false, NAME, ": unsupported dtype ", TYPE);             \
+    }                                                                       \
+  }()
+
+// What the dual kernels take: a non-empty dense channels-last 4-D bf16 / half
+// tensor on the GPU with C a multiple of 8.  Alignment is the plans' business.
+bool dual_tensor_ok(const at::Tensor& x) {
+  if (!x.is_cuda() || x.dim() != 4 || x.numel() == 0) return false;
+  if (x.scalar_type() != at::kBFloat16 && x.scalar_type() != at::kHalf)
+    return false;
+  if (x.suggest_memory_format() != at::MemoryFormat::ChannelsLast ||
+      !x.is_contiguous(at::MemoryFormat::ChannelsLast))
+    return false;
+  return x.size(1) % 8 == 0;
+}
+
+bool dual_same(const at::Tensor& t, const at::Tensor& x) {
+  return t.defined() && t.sizes() == x.sizes() && t.strides() == x.strides() &&
+         t.scalar_type() == x.scalar_type() && t.device() == x.device();
+}
+
+bool dual_coef_ok(const at::Tensor& c, int64_t rows, int64_t C,
+                  const at::Tensor& x) {
+  return c.defined() && c.scalar_type() == at::kFloat && c.is_contiguous() &&
+         c.numel() == rows * C && c.device() == x.device() &&
+         ((uintptr_t)c.data_ptr() % (8 * sizeof(float))) == 0;
+}
+
+// The reduce runs on the plan the single gated reduce takes for these
+// pointers (x2 is one more pack pointer); declined unless that is V = 8.
+bool dual_reduce_plan(const at::Tensor& x, const at::Tensor& x2,
+                      const at::Tensor& dy, const at::Tensor& gm,
+                      const c10::optional<at::Tensor>& dy2, ReducePlan* out) {
+  if (!dual_tensor_ok(x) || !dual_same(x2, x) || !dual_same(dy, x) ||
+      !dual_same(gm, x))
+    return false;
+  if (dy2.has_value() && !dual_same(*dy2, x)) return false;
+  const Layout L = get_layout(x);
+  const ReducePlan p = plan_reduce(
+      L, 2,
+      {x.data_ptr(), dy.data_ptr(), x2.data_ptr(), gm.data_ptr(),
+       dy2.has_value() ? dy2->data_ptr() : nullptr});
+  if (p.path != RedPath::Nhwc || p.v != 8) return false;
+  *out = p;
+  return true;
+}
+
+bool dual_elemt_plan(const at::Tensor& x,
+                     c10::ArrayRef<const at::Tensor*> same, ElemtPlan* out) {
+  if (!dual_tensor_ok(x)) return false;
+  std::vector<const void*> ptrs{x.data_ptr()};
+  for (const at::Tensor* t : same) {
+    if (!dual_same(*t, x)) return false;
+    ptrs.push_back(t->data_ptr());
+  }
+  const ElemtPlan p = plan_elemt(get_layout(x), x.numel(), 2, ptrs, nullptr);
+  if (p.v != 8) return false;
+  *out = p;
+  return true;
+}
+}  // namespace
+
+std::tuple<at::Tensor, bool> batch_norm_elemt_act_dual(
+    const at::Tensor& input, const at::Tensor& input2, const at::Tensor& coefs,
+    const at::Tensor& coefs2, bool relu, double negative_slope,
+    const at::Tensor& gate_out) {
+  ElemtPlan plan{};
+  if (!relu || negative_slope != 0.0 ||
+      !dual_elemt_plan(input, {&input2}, &plan))
+    return {at::Tensor(), false};
+  const int64_t C = input.size(1);
+  if (!dual_coef_ok(coefs, 2, C, input) || !dual_coef_ok(coefs2, 2, C, input))
+    return {at::Tensor(), false};
+  check_gate_tensor(gate_out, input, "gate_out");
+  auto out = at::empty_like(input);  // allocator-aligned
+  const int64_t total = input.numel();
+  auto stream = cur_stream();
+  const float* sc = coefs.data_ptr<float>();
+  const float* sc2 = coefs2.data_ptr<float>();
+  MSBN_DISPATCH_HALF_TYPES(input.scalar_type(), "bn_elemt_dual", [&] {
+    hipLaunchKernelGGL(
+        (bn_elemt_dual_nhwc<native_t>), dim3(plan.grid), dim3(MSBN_BLOCK), 0,
+        stream, reinterpret_cast<const native_t*>(input.data_ptr()),
+        reinterpret_cast<const native_t*>(input2.data_ptr()),
+        reinterpret_cast<native_t*>(out.data_ptr()), sc, sc + C, sc2, sc2 + C,
+        total, C, gate_out.data_ptr<unsigned char>());
+  });
+  return {out, true};
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor>
+batch_norm_backward_reduce_act_dual(
+    const at::Tensor& grad_out, const at::Tensor& input,
+    const at::Tensor& input2, const at::Tensor& mean, const at::Tensor& mean2,
+    const at::Tensor& invstd, const at::Tensor& invstd2,
+    const c10::optional<at::Tensor>& weight,
+    const c10::optional<at::Tensor>& weight2, bool weight_g, bool bias_g,
+    bool weight2_g, bool bias2_g, const at::Tensor& gm_out,
+    const c10::optional<at::Tensor>& grad_out2, const at::Tensor& gate) {
+  TORCH_CHECK(input.dim() >= 2 && input2.sizes() == input.sizes(),
+              "input2 must match input");
+  const int64_t C = input.size(1);
+  auto f32 = input.options().dtype(at::kFloat);
+  ReducePlan plan{};
+  if (!dual_reduce_plan(input, input2, grad_out, gm_out, grad_out2, &plan)) {
+    // declined (a gradient off alignment, ...): the composition's two
+    // reduces, packed into the same message
+    auto r1 = msbn::batch_norm_backward_reduce_act(
+        grad_out, input, c10::nullopt, mean, invstd, weight, c10::nullopt,
+        true, true, weight_g, bias_g, c10::nullopt, gm_out, 0.0, grad_out2,
+        gate);
+    auto r2 = msbn::batch_norm_backward_reduce(
+        gm_out, input2, mean2, invstd2, weight2, true, weight2_g, bias2_g);
+    auto sums = at::cat({std::get<0>(r1), std::get<1>(r1), std::get<0>(r2),
+                         std::get<1>(r2)});
+    return {sums, std::get<2>(r1), std::get<3>(r1), std::get<2>(r2),
+            std::get<3>(r2)};
+  }
+  check_gate_tensor(gate, input, "gate");
+  const Layout L = get_layout(input);
+  // ONE contiguous buffer [sum_dy | sum_dy_xmu | sum_dy_2 | sum_dy_xmu_2]
+  auto sums = at::empty({4 * C}, f32);
+  float* sp = sums.data_ptr<float>();
+  auto affine = [&](const c10::optional<at::Tensor>& w, bool on) {
+    return on ? at::empty({C}, input.options().dtype(
+                                   w.has_value() ? w->scalar_type()
+                                                 : input.scalar_type()))
+              : at::Tensor();
+  };
+  at::Tensor gw = affine(weight, weight_g), gb = affine(weight, bias_g);
+  at::Tensor gw2 = affine(weight2, weight2_g), gb2 = affine(weight2, bias2_g);
+  const int nchunks = plan.nchunks;
+  at::Tensor ws = at::empty({2, (int64_t)nchunks * C * 2},
+                            input.options().dtype(at::kDouble));
+  double* ws1 = ws.data_ptr<double>();
+  double* ws2 = ws1 + (int64_t)nchunks * C * 2;
+  const bool has_dy2 = grad_out2.has_value();
+  auto stream = cur_stream();
+  MSBN_DISPATCH_HALF_TYPES(input.scalar_type(), "bn_bwd_reduce_dual", [&] {
+    const auto& g = plan.nhwc;
+    MSBN_DISPATCH_BOOL(has_dy2, DY2_, [&] {
+      hipLaunchKernelGGL(
+          (bn_bwd_reduce_dual_partial_nhwc<native_t, DY2_>), g.grid,
+          dim3(MSBN_BLOCK), 0, stream,
+          reinterpret_cast<const native_t*>(grad_out.data_ptr()),
+          has_dy2 ? reinterpret_cast<const native_t*>(grad_out2->data_ptr())
+                  : nullptr,
+          reinterpret_cast<const native_t*>(input.data_ptr()),
+          reinterpret_cast<const native_t*>(input2.data_ptr()),
+          reinterpret_cast<native_t*>(gm_out.data_ptr()),
+          mean.data_ptr<float>(), mean2.data_ptr<float>(), ws1, ws2, L.rows,
+          L.C, g.chunk_rows, g.lpr, gate.data_ptr<unsigned char>());
+    });
+  });
+  const int fgrid = (int)cdiv(C, kFinalizeWavesPerBlock);
+  auto finalize = [&](const double* w, const at::Tensor& istd, float* s,
+                      at::Tensor& gwt, at::Tensor& gbt, at::ScalarType wt) {
+    MSBN_DISPATCH_RSTAT(wt, "bn_bwd_reduce_dual", [&] {
+      hipLaunchKernelGGL(
+          (bn_bwd_reduce_finalize<rstat_t>), dim3(fgrid), dim3(MSBN_BLOCK), 0,
+          stream, w, nchunks, C, istd.data_ptr<float>(), s, s + C,
+          gwt.defined() ? reinterpret_cast<rstat_t*>(gwt.data_ptr()) : nullptr,
+          gbt.defined() ? reinterpret_cast<rstat_t*>(gbt.data_ptr())
+                        : nullptr);
+    });
+  };
+  finalize(ws1, invstd, sp, gw, gb,
+           weight.has_value() ? weight->scalar_type() : input.scalar_type());
+  finalize(ws2, invstd2, sp + 2 * C, gw2, gb2,
+           weight2.has_value() ? weight2->scalar_type() : input.scalar_type());
+  return {sums, gw, gb, gw2, gb2};
+}
+
+std::tuple<at::Tensor, at::Tensor> batch_norm_backward_elemt_dual(
+    const at::Tensor& gm, const at::Tensor& input, const at::Tensor& input2,
+    const at::Tensor& mean, const at::Tensor& mean2, const at::Tensor& invstd,
+    const at::Tensor& invstd2, const c10::optional<at::Tensor>& weight,
+    const c10::optional<at::Tensor>& weight2, const at::Tensor& sums,
+    const at::Tensor& count) {
+  ElemtPlan plan{};
+  TORCH_CHECK(dual_elemt_plan(input, {&input2, &gm}, &plan),
+              "batch_norm_backward_elemt_dual: needs dense channels-last "
+              "bf16 / half tensors, C a multiple of 8, 16-byte aligned");
+  const int64_t C = input.size(1);
+  TORCH_CHECK(sums.scalar_type() == at::kFloat && sums.is_contiguous() &&
+                  sums.numel() == 4 * C,
+              "sums must be the contiguous fp32 [4C] buffer of the dual "
+              "reduce");
+  auto dx = at::empty_like(input);
+  auto dx2 = at::empty_like(input);
+  at::Tensor count_sum;
+  if (count.numel() == 1 && count.scalar_type() == at::kFloat) {
+    count_sum = count;
+  } else {
+    count_sum = count.to(at::kFloat).sum().reshape({1});
+  }
+  auto stream = cur_stream();
+  // [a | b | d] of the main layer, then of the skip layer (allocator-aligned;
+  // 3C floats is a multiple of 32 bytes since C % 8 == 0)
+  auto co = at::empty({6 * C}, input.options().dtype(at::kFloat));
+  float* co1 = co.data_ptr<float>();
+  float* co2 = co1 + 3 * C;
+  const float* sp = sums.data_ptr<float>();
+  const int cgrid = (int)cdiv(C, MSBN_BLOCK);
+  auto affine = [&](const at::Tensor& mu, const at::Tensor& istd,
+                    const c10::optional<at::Tensor>& w, const float* s,
+                    float* o) {
+    const auto wtype = w.has_value() ? w->scalar_type() : at::kFloat;
+    MSBN_DISPATCH_RSTAT(wtype, "bn_bwd_elemt_dual", [&] {
+      hipLaunchKernelGGL(
+          (bn_affine_bwd<rstat_t>), dim3(cgrid), dim3(MSBN_BLOCK), 0, stream,
+          mu.data_ptr<float>(), istd.data_ptr<float>(),
+          w.has_value() ? reinterpret_cast<const rstat_t*>(w->data_ptr())
+                        : nullptr,
+          s, s + C, count_sum.data_ptr<float>(), C, o, o + C, o + 2 * C);
+    });
+  };
+  affine(mean, invstd, weight, sp, co1);
+  affine(mean2, invstd2, weight2, sp + 2 * C, co2);
+  MSBN_DISPATCH_HALF_TYPES(input.scalar_type(), "bn_bwd_elemt_dual", [&] {
+    hipLaunchKernelGGL(
+        (bn_bwd_elemt_dual_nhwc<native_t>), dim3(plan.grid), dim3(MSBN_BLOCK),
+        0, stream, reinterpret_cast<const native_t*>(gm.data_ptr()),
+        reinterpret_cast<const native_t*>(input.data_ptr()),
+        reinterpret_cast<const native_t*>(input2.data_ptr()),
+        reinterpret_cast<native_t*>(dx.data_ptr()),
+        reinterpret_cast<native_t*>(dx2.data_ptr()), co1, co2, input.numel(),
+        C);
+  });
+  return {dx, dx2};
+}
+
+// ---------------------------------------------------------------------------
 // launch_plan: host-only; launches nothing.  Reports, from the SAME helpers
 // the ops launch with (get_layout, plan_reduce / plan_elemt -> pick_v, *_grid,
 // bn_fused_local_eligible), which kernel path a call would take and how far
@@ -3883,6 +4356,53 @@ std::tuple<std::string, std::map<std::string, int64_t>> launch_plan(
                           : nullptr;
   std::map<std::string, int64_t> d;
   std::string path;
+
+  // dual BN: the single counterparts' numbers plus "dual", or "ineligible"
+  // where the ops decline and the composition runs
+  if (kind == "elemt_dual" || kind == "bwd_elemt_dual") {
+    // elemt_dual: others = {x2[, coefs2]}; bwd_elemt_dual: others = {gm, x2}
+    const bool fwd = kind == "elemt_dual";
+    ElemtPlan p{};
+    bool ok = given(0);
+    if (ok && fwd) {
+      const int64_t C = input.size(1);
+      ok = dual_elemt_plan(input, {&*others[0]}, &p) &&
+           (!coefs.has_value() || dual_coef_ok(*coefs, 2, C, input)) &&
+           (!given(1) || dual_coef_ok(*others[1], 2, C, input));
+    } else if (ok) {
+      ok = given(1) && dual_elemt_plan(input, {&*others[0], &*others[1]}, &p);
+    }
+    if (!ok) return {"ineligible", d};
+    const int64_t threads = (int64_t)p.grid * MSBN_BLOCK;
+    d["V"] = p.v;
+    d["grid"] = p.grid;
+    d["packs"] = p.packs;
+    d["trips"] = cdiv(p.packs, threads);
+    d["multi_trip"] = p.packs > threads ? 1 : 0;
+    d["dual"] = 1;
+    return {"nhwc", d};
+  }
+  if (kind == "bwd_reduce_dual") {
+    // others = {grad_out, x2, gm_out, grad_out2, gate}
+    ReducePlan p{};
+    const bool ok =
+        given(0) && given(1) && given(2) && given(4) &&
+        dual_reduce_plan(input, *others[1], *others[0], *others[2],
+                         given(3) ? others[3] : c10::optional<at::Tensor>(),
+                         &p);
+    if (!ok) return {"ineligible", d};
+    d["V"] = p.v;
+    d["nchunks"] = p.nchunks;
+    d["trips"] = p.trips;
+    d["flush_every"] = p.flush_every;
+    d["finalize_trips"] = cdiv(p.nchunks, MSBN_WAVE);
+    d["chunk_rows"] = p.nhwc.chunk_rows;
+    d["lpr"] = p.nhwc.lpr;
+    d["ctiles"] = p.nhwc.grid.x;
+    d["gate"] = 1;
+    d["dual"] = 1;
+    return {"nhwc", d};
+  }
 
   if (kind == "fused_local") {
     if (!bn_fused_local_eligible(input, c10::nullopt, c10::nullopt,

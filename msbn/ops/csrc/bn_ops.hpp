@@ -255,6 +255,46 @@ at::Tensor batch_norm_backward_elemt_inplace(
     const at::Tensor& sum_dy_xmu, const at::Tensor& count, bool act,
     const c10::optional<at::Tensor>& coefs_in, double negative_slope);
 
+// ---- dual BN: relu(bn(x) + bn_d(x_d)) in three kernels ---------------------
+// The first block of a ResNet stage normalises its skip path too.  These ops
+// run the pair of layers with one forward kernel, one backward reduce and one
+// backward elemt kernel: the skip BN's output is never stored and gm is read
+// once per pass for both layers.  Dense channels-last 4-D bf16 / half, C a
+// multiple of 8, 16-byte aligned tensors, plain ReLU, gate bits.  Results are
+// bit-identical to batch_norm_elemt + batch_norm_elemt_act(residual,
+// gate_out) / the gated reduce + batch_norm_backward_reduce on gm / two
+// batch_norm_backward_elemt calls.
+//
+// coefs / coefs2: packed [scale | shift] of the main / skip layer.  Returns
+// (y, stored); stored == false means the kernel declined: y is undefined and
+// nothing was written (gate_out included).
+std::tuple<at::Tensor, bool> batch_norm_elemt_act_dual(
+    const at::Tensor& input, const at::Tensor& input2, const at::Tensor& coefs,
+    const at::Tensor& coefs2, bool relu, double negative_slope,
+    const at::Tensor& gate_out);
+
+// (sums, grad_weight, grad_bias, grad_weight2, grad_bias2); sums is ONE
+// contiguous fp32 [4C] buffer [sum_dy | sum_dy_xmu | sum_dy_2 | sum_dy_xmu_2]
+// (a single all_reduce for the pair).  gm_out receives the gated gradient.
+// Inputs the dual kernel declines run the two single reduces instead.
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor>
+batch_norm_backward_reduce_act_dual(
+    const at::Tensor& grad_out, const at::Tensor& input,
+    const at::Tensor& input2, const at::Tensor& mean, const at::Tensor& mean2,
+    const at::Tensor& invstd, const at::Tensor& invstd2,
+    const c10::optional<at::Tensor>& weight,
+    const c10::optional<at::Tensor>& weight2, bool weight_g, bool bias_g,
+    bool weight2_g, bool bias2_g, const at::Tensor& gm_out,
+    const c10::optional<at::Tensor>& grad_out2, const at::Tensor& gate);
+
+// (dx, dx2) from one read of gm; sums is the [4C] buffer above.
+std::tuple<at::Tensor, at::Tensor> batch_norm_backward_elemt_dual(
+    const at::Tensor& gm, const at::Tensor& input, const at::Tensor& input2,
+    const at::Tensor& mean, const at::Tensor& mean2, const at::Tensor& invstd,
+    const at::Tensor& invstd2, const c10::optional<at::Tensor>& weight,
+    const c10::optional<at::Tensor>& weight2, const at::Tensor& sums,
+    const at::Tensor& count);
+
 // ---- launch plan (host only, launches nothing) ----------------------------
 // Which kernel path a call would take and how far its loops run, decided by
 // the same host code the ops launch with.  kind / tensors:
@@ -272,8 +312,14 @@ at::Tensor batch_norm_backward_elemt_inplace(
 //   "bwd_reduce_pool"    input = x,      others = {grad_out, grad_out2, codes}
 //   "bwd_elemt_pool"     input = x,      others = {grad_out, grad_out2, codes},
 //                                        coefs
+//   "elemt_dual"         input = x,      others = {x2[, coefs2]}, coefs
+//   "bwd_reduce_dual"    input = x,      others = {grad_out, x2, gm_out,
+//                                                  grad_out2, gate}
+//   "bwd_elemt_dual"     input = x,      others = {gm, x2}
 // (pass only what the op itself would dereference).  Returns (path, numbers):
 // path is "nchw_vec" | "nchw_flat" | "nhwc" | "small_plane" | "ineligible";
+// the dual kinds report "nhwc" with their single counterparts' numbers plus
+// dual = 1, or "ineligible" for inputs the dual kernels decline;
 // numbers always hold V and trips (most loop iterations of one thread);
 // reductions add nchunks, flush_every, finalize_trips and the chunk sizes,
 // elementwise ops add grid, packs and multi_trip.

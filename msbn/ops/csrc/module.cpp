@@ -100,6 +100,24 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("sum_dy_xmu"), py::arg("count"), py::arg("act"),
         py::arg("coefs") = py::none(), py::arg("negative_slope") = 0.0);
 
+  m.def("batch_norm_elemt_act_dual", &msbn::batch_norm_elemt_act_dual,
+        py::arg("input"), py::arg("input2"), py::arg("coefs"),
+        py::arg("coefs2"), py::arg("relu"), py::arg("negative_slope"),
+        py::arg("gate_out"));
+  m.def("batch_norm_backward_reduce_act_dual",
+        &msbn::batch_norm_backward_reduce_act_dual, py::arg("grad_out"),
+        py::arg("input"), py::arg("input2"), py::arg("mean"),
+        py::arg("mean2"), py::arg("invstd"), py::arg("invstd2"),
+        py::arg("weight"), py::arg("weight2"), py::arg("weight_g"),
+        py::arg("bias_g"), py::arg("weight2_g"), py::arg("bias2_g"),
+        py::arg("gm_out"), py::arg("grad_out2"), py::arg("gate"));
+  m.def("batch_norm_backward_elemt_dual",
+        &msbn::batch_norm_backward_elemt_dual, py::arg("gm"),
+        py::arg("input"), py::arg("input2"), py::arg("mean"),
+        py::arg("mean2"), py::arg("invstd"), py::arg("invstd2"),
+        py::arg("weight"), py::arg("weight2"), py::arg("sums"),
+        py::arg("count"));
+
   m.def("bn_frozen_coefs", &msbn::bn_frozen_coefs, py::arg("running_mean"),
         py::arg("running_var"), py::arg("eps"), py::arg("weight"),
         py::arg("bias"));

@@ -14,6 +14,9 @@ Cases (argv[1]):
            collectives inside the graph; replays must track an eager clone.
   gate   — one bn+add+relu layer under forced sync, gate bits on and off:
            bit-equal results, the bits saved in place of the residual.
+  dual   — a closing bn+add+relu whose skip path has a BatchNorm of its own,
+           as one dual layer and as the composition: bit-equal results, and
+           (with MSBN_COMM_LOG=1) ONE [4C] backward all_reduce for the pair.
 
 Run standalone (a known ROCm issue segfaults hipGraph capture inside the
 pytest host process — see tests/test_gpu_fused.py::test_graphed_step_gpu).
@@ -243,6 +246,66 @@ def case_gate():
     print("CASE gate OK")
 
 
+def case_dual():
+    """bn_add_bn_act against bn(x, residual=bn_skip(x_d)) under forced sync:
+    the statistics and the backward sums go through RCCL on both routes; the
+    dual route sends the two layers' sums as one [4C] message."""
+    import msbn.nn.fused as fused_mod
+    from msbn.nn import SyncBatchNorm
+    from msbn.nn.fused import SyncBatchNormAct2d, bn_add_bn_act
+    from msbn.utils.logging import comm_log
+
+    cl = torch.channels_last
+    C = 16
+    g = torch.Generator(device="cuda").manual_seed(5)
+
+    def rand():
+        return torch.randn(4, C, 6, 6, generator=g, device="cuda") \
+            .bfloat16().contiguous(memory_format=cl)
+
+    x, x_d, dy = rand() + 1, rand() * 2 - 1, rand()
+    w = [torch.randn(C, generator=g, device="cuda") for _ in range(4)]
+    stored = []
+    real = fused_mod.ops.batch_norm_elemt_act_dual
+
+    def spy(*a, **kw):
+        out_ = real(*a, **kw)
+        stored.append(out_[1])
+        return out_
+
+    fused_mod.ops.batch_norm_elemt_act_dual = spy
+    out, logs = [], []
+    for dual in (True, False):
+        bn = SyncBatchNormAct2d(C).cuda().train()
+        bn_skip = SyncBatchNorm(C).cuda().train()
+        with torch.no_grad():
+            bn.weight.copy_(w[0].abs() + 0.1), bn.bias.copy_(w[1])
+            bn_skip.weight.copy_(w[2].abs() + 0.1), bn_skip.bias.copy_(w[3])
+        xi = x.clone().requires_grad_(True)
+        di = x_d.clone().requires_grad_(True)
+        comm_log.buf.clear()
+        if dual:
+            y = bn_add_bn_act(bn, bn_skip, xi, di)
+        else:
+            y = bn(xi, residual=bn_skip(di))
+        y.backward(dy)
+        logs.append([(op, b) for _, op, b, _ in comm_log.buf])
+        out.append((y.detach(), xi.grad, di.grad, bn.weight.grad,
+                    bn.bias.grad, bn_skip.weight.grad, bn_skip.bias.grad,
+                    bn.running_mean, bn.running_var, bn_skip.running_mean,
+                    bn_skip.running_var))
+    fused_mod.ops.batch_norm_elemt_act_dual = real
+    assert stored == [True], stored
+    for a, b in zip(*out):
+        assert torch.equal(a, b)
+    if comm_log.enabled:
+        gather = ("all_gather", (2 * C + 1) * 4)
+        assert logs[0] == [gather, gather, ("all_reduce", 4 * C * 4)], logs[0]
+        assert logs[1] == [gather, gather, ("all_reduce", 2 * C * 4),
+                           ("all_reduce", 2 * C * 4)], logs[1]
+    print("CASE dual OK")
+
+
 def main():
     case = sys.argv[1] if len(sys.argv) > 1 else "ddp"
     torch.cuda.set_device(0)
@@ -258,6 +321,8 @@ def main():
             case_stress()
         elif case == "gate":
             case_gate()
+        elif case == "dual":
+            case_dual()
         else:
             raise SystemExit(f"unknown case {case}")
     finally:
