@@ -16,8 +16,8 @@ import torch
 import torch.nn as nn
 
 from msbn.nn import BatchNorm2d, SyncBatchNorm
-from msbn.nn.fused import (SyncBatchNormAct2d, bn_act_maxpool,
-                           bn_add_bn_act)
+from msbn.nn.fused import (SyncBatchNormAct2d, _bn_call, bn_act_maxpool,
+                           bn_add_bn_act, conv1x1_bn_act, conv1x1_with_stats)
 
 
 def conv3x3(cin, cout, stride=1):
@@ -68,24 +68,50 @@ def _dual_downsample(block):
     )
 
 
+def _conv_stats(block):
+    # the 1x1 convolutions of a fused block emit their BatchNorm's statistics
+    return block.fused and getattr(block, "conv_stats", False)
+
+
 def _skip_path(block, skip):
     """``(identity, x_d)`` of a block.  On the dual route the skip path stops
     after its conv (where it has always run, ahead of conv1): ``identity`` is
-    None and ``x_d`` goes to ``_close`` unnormalised."""
+    None and ``x_d`` goes to ``_close`` unnormalised -- with ``conv_stats``
+    as the ``(x_d, partials)`` pair of ``conv1x1_with_stats``."""
+    d = block.downsample
     if _dual_downsample(block):
-        return None, block.downsample[0](skip)
-    if block.downsample is not None:
-        return block.downsample(skip), None
+        if _conv_stats(block):
+            return None, conv1x1_with_stats(d[0], d[1], skip)
+        return None, d[0](skip)
+    if d is not None:
+        if (_conv_stats(block) and type(d) is nn.Sequential and len(d) == 2
+                and type(d[1]) is SyncBatchNorm
+                and not (d._forward_hooks or d._forward_pre_hooks
+                         or d._backward_hooks or d._backward_pre_hooks)):
+            return conv1x1_bn_act(d[0], d[1], skip), None
+        return d(skip), None
     return skip, None
 
 
-def _close(block, bn, x, identity, x_d):
-    """The block's closing bn(+add)+relu over the conv output ``x``."""
+def _close(block, bn, x, identity, x_d, conv=None):
+    """The block's closing bn(+add)+relu over the conv output ``x``; with
+    ``conv`` (``conv_stats``), over ``conv(x)``, the 1x1 convolution emitting
+    the statistics where it can."""
     fork = getattr(block, "fork", False)
+    partials = partials_d = None
+    if conv is not None:
+        x, partials = conv1x1_with_stats(conv, bn, x)
+    if isinstance(x_d, tuple):
+        x_d, partials_d = x_d
     if identity is None:
         if isinstance(bn, SyncBatchNormAct2d):
-            return bn_add_bn_act(bn, block.downsample[1], x, x_d, fork)
+            if partials is None and partials_d is None:
+                return bn_add_bn_act(bn, block.downsample[1], x, x_d, fork)
+            return bn_add_bn_act(bn, block.downsample[1], x, x_d, fork,
+                                 partials=partials, partials_skip=partials_d)
         identity = block.downsample[1](x_d)
+    if partials is not None:
+        return _bn_call(bn, x, identity, fork, partials)
     return _last_bn(bn, x, identity, fork)
 
 
@@ -131,11 +157,18 @@ class Bottleneck(nn.Module):
     expansion = 4
 
     def __init__(self, cin, planes, stride=1, downsample=None, fused=False,
-                 fork=False, gate_bits=True, dual_bn=True):
+                 fork=False, gate_bits=True, dual_bn=True, conv_stats=False):
         super().__init__()
         self.fused = fused
         self.fork = fork and fused  # as in BasicBlock
         self.dual_bn = dual_bn and gate_bits and fused  # as in BasicBlock
+        # fused only: conv1 -> bn1, conv3 -> bn3 and a stride-1 (Conv2d,
+        # SyncBatchNorm) downsample run the 1x1 convolution as the kernel
+        # that also emits the BatchNorm's statistics (msbn/nn/fused.py
+        # conv1x1_bn_act), which falls back to the composition for anything
+        # it does not take.  Off by default: the convolution's output is
+        # not bit-identical to the stock one.
+        self.conv_stats = conv_stats and fused
         self.conv1 = conv1x1(cin, planes)
         self.conv2 = conv3x3(planes, planes, stride)
         self.conv3 = conv1x1(planes, planes * self.expansion)
@@ -154,6 +187,10 @@ class Bottleneck(nn.Module):
     def forward(self, x):
         x, skip = _split(x)
         identity, x_d = _skip_path(self, skip)
+        if _conv_stats(self):
+            out = conv1x1_bn_act(self.conv1, self.bn1, x)
+            out = self.bn2(self.conv2(out))
+            return _close(self, self.bn3, out, identity, x_d, self.conv3)
         if self.fused:
             out = self.bn1(self.conv1(x))
             out = self.bn2(self.conv2(out))
@@ -175,9 +212,13 @@ class ResNet(nn.Module):
         fork_grads: bool = True,
         gate_bits: bool = True,
         dual_bn: bool = True,
+        conv_stats: bool = False,
     ):
         super().__init__()
         self.fused = fused
+        # fused Bottleneck models: the 1x1 stride-1 convolutions emit the
+        # statistics of the BatchNorm after them (Bottleneck.conv_stats)
+        self.conv_stats = conv_stats and fused and block is Bottleneck
         # fused models with gate bits: the first block of a stage runs its
         # downsample BatchNorm inside the closing BN's kernels (dual BN,
         # msbn/nn/fused.py bn_add_bn_act).  Same math either way; False
@@ -223,13 +264,16 @@ class ResNet(nn.Module):
                 conv1x1(self.inplanes, planes * block.expansion, stride),
                 _norm(planes * block.expansion, self.fused),
             )
+        extra = {"conv_stats": True} if self.conv_stats else {}
         layers = [block(self.inplanes, planes, stride, downsample,
                         fused=self.fused, fork=fork[0],
-                        gate_bits=self.gate_bits, dual_bn=self.dual_bn)]
+                        gate_bits=self.gate_bits, dual_bn=self.dual_bn,
+                        **extra)]
         self.inplanes = planes * block.expansion
         for i in range(1, blocks):
             layers.append(block(self.inplanes, planes, fused=self.fused,
-                                fork=fork[i], gate_bits=self.gate_bits))
+                                fork=fork[i], gate_bits=self.gate_bits,
+                                **extra))
         return nn.Sequential(*layers)
 
     def _stem(self, x):
@@ -275,7 +319,7 @@ def resnet18(num_classes: int = 1000, fused: bool = False,
 
 def resnet50(num_classes: int = 1000, fused: bool = False,
              fork_grads: bool = True, gate_bits: bool = True,
-             dual_bn: bool = True) -> ResNet:
+             dual_bn: bool = True, conv_stats: bool = False) -> ResNet:
     return ResNet(Bottleneck, [3, 4, 6, 3], num_classes, fused=fused,
                   fork_grads=fork_grads, gate_bits=gate_bits,
-                  dual_bn=dual_bn)
+                  dual_bn=dual_bn, conv_stats=conv_stats)

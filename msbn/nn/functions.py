@@ -98,19 +98,30 @@ def compute_sync_stats(
     weight: Optional[torch.Tensor] = None,
     bias: Optional[torch.Tensor] = None,
     want_coefs: bool = False,
+    partials: Optional[torch.Tensor] = None,
+    nchunks: Optional[int] = None,
 ):
     """Local packed moments -> all_gather over RCCL/xGMI (S5) -> counts-weighted
     combine with in-kernel zero-count masking + running-stats update.  The
     combine/finalize kernel also emits the per-channel [scale|shift] coefs
     when requested (one launch for the whole per-layer channel math).
-    Returns (mean, invstd, count_sum[1], coefs-or-None)."""
+    Returns (mean, invstd, count_sum[1], coefs-or-None).
+
+    ``partials`` / ``nchunks``: the fp64 workspace ``ops.conv1x1_stats``
+    filled while it produced ``input`` (a non-empty GPU tensor).  The local
+    moments are then finalized from it and ``input`` is not read; the
+    collectives and everything after them are the same."""
     C = int(input.shape[1])
     local_count = input.numel() // C if C > 0 else 0
     on_gpu = input.is_cuda
 
     if world_size > 1 or (process_group is not None and _force_sync()):
         packed = torch.empty(2 * C + 1, dtype=torch.float32, device=input.device)
-        if local_count > 0:
+        if partials is not None:
+            ops.batch_norm_stats_packed_from_partials(
+                partials, nchunks, local_count, eps, packed
+            )
+        elif local_count > 0:
             ops.batch_norm_stats_packed(input, eps, packed)
         else:
             packed.zero_()
@@ -146,6 +157,12 @@ def compute_sync_stats(
             input, packed_all, running_mean, running_var, momentum, eps
         )
         return mean, invstd, count_sum, None
+
+    if partials is not None:
+        return ops.batch_norm_stats_local_from_partials(
+            partials, nchunks, local_count, eps, running_mean, running_var,
+            momentum, weight, bias, want_coefs,
+        )
 
     if on_gpu and local_count > 0:
         from msbn.ops import _require_hip

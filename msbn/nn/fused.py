@@ -46,8 +46,16 @@ class SyncBatchNormActFunction(torch.autograd.Function):
         negative_slope: float = 0.0,
         fork: bool = False,
         gate_bits: bool = False,
+        partials: Optional[torch.Tensor] = None,
+        nchunks: Optional[int] = None,
     ):
-        """``fork=True`` returns the output twice — ``(y, y.detach())``, two
+        """``partials`` / ``nchunks``: ``input`` came out of
+        ``ops.conv1x1_stats`` together with these per-channel partial sums;
+        the statistics are finalized from them instead of read from
+        ``input`` (``compute_sync_stats``), always on the two-stage route.
+        Everything after the statistics is the same.
+
+        ``fork=True`` returns the output twice — ``(y, y.detach())``, two
         tensor objects over one storage, no copy — for a result that feeds
         two consumers (a residual block's conv1 and its skip path).  Autograd
         sums gradients per output edge, so two outputs are what lets
@@ -67,6 +75,7 @@ class SyncBatchNormActFunction(torch.autograd.Function):
         y = SyncBatchNormActFunction._forward(
             ctx, input, residual, weight, bias, running_mean, running_var,
             eps, momentum, process_group, world_size, relu, negative_slope,
+            partials, nchunks,
         )
         if not fork:
             return y
@@ -77,7 +86,7 @@ class SyncBatchNormActFunction(torch.autograd.Function):
     @staticmethod
     def _forward(ctx, input, residual, weight, bias, running_mean,
                  running_var, eps, momentum, process_group, world_size, relu,
-                 negative_slope):
+                 negative_slope, partials=None, nchunks=None):
         ctx.negative_slope = negative_slope
         ctx.has_res = residual is not None
         ctx.has_gate = False
@@ -94,6 +103,7 @@ class SyncBatchNormActFunction(torch.autograd.Function):
         )
         if (
             not use_sync
+            and partials is None  # the statistics exist already
             and input.numel() > 0
             and (residual is None or residual.is_contiguous())
             and ops.bn_fused_local_eligible(
@@ -122,6 +132,7 @@ class SyncBatchNormActFunction(torch.autograd.Function):
         mean, invstd, count_sum, coefs = compute_sync_stats(
             input, eps, momentum, running_mean, running_var,
             process_group, world_size, weight, bias, want_coefs=True,
+            partials=partials, nchunks=nchunks,
         )
         ctx.has_coefs = coefs is not None
         ctx.relu = relu
@@ -160,7 +171,7 @@ class SyncBatchNormActFunction(torch.autograd.Function):
         if grad_output is None:  # fork with only the second output used
             grad_output, grad_skip = grad_skip, None
         if grad_output is None:
-            return (None,) * 14
+            return (None,) * 16
         saved = ctx.saved_tensors
         input, residual, weight, bias, mean, invstd, count_sum = saved[:7]
         coefs = saved[7] if ctx.has_coefs else None
@@ -217,6 +228,7 @@ class SyncBatchNormActFunction(torch.autograd.Function):
                 grad_weight if need_weight_g else None,
                 grad_bias if need_bias_g else None,
                 None, None, None, None, None, None, None, None, None, None,
+                None, None,
             )
 
         # Masked-grad materialization: when the residual branch needs its
@@ -250,6 +262,7 @@ class SyncBatchNormActFunction(torch.autograd.Function):
                 torch.zeros_like(weight) if need_weight_g else None,
                 torch.zeros_like(bias) if need_bias_g else None,
                 None, None, None, None, None, None, None, None, None, None,
+                None, None,
             )
         gm = torch.empty_like(grad_output) if use_gm else None
         if gate is not None:
@@ -301,6 +314,7 @@ class SyncBatchNormActFunction(torch.autograd.Function):
             grad_weight if need_weight_g else None,
             grad_bias if need_bias_g else None,
             None, None, None, None, None, None, None, None, None, None,
+            None, None,
         )
 
 
@@ -521,7 +535,10 @@ class SyncBatchNormDualActFunction(torch.autograd.Function):
     def forward(ctx, input, input2, weight, bias, weight2, bias2,
                 running_mean, running_var, running_mean2, running_var2,
                 eps: float, eps2: float, momentum: float, momentum2: float,
-                process_group, world_size: int, fork: bool = False):
+                process_group, world_size: int, fork: bool = False,
+                partials=None, nchunks=None, partials2=None, nchunks2=None):
+        # partials / partials2: the conv1x1_stats workspaces of input /
+        # input2, each optional on its own (compute_sync_stats)
         x = _contig(input)
         x2 = _contig(input2)
         weight, bias, weight2, bias2 = (
@@ -534,6 +551,7 @@ class SyncBatchNormDualActFunction(torch.autograd.Function):
         mean2, invstd2, count2, coefs2 = compute_sync_stats(
             x2, eps2, momentum2, running_mean2, running_var2,
             process_group, world_size, weight2, bias2, want_coefs=True,
+            partials=partials2, nchunks=nchunks2,
         )
         # x and x_skip have one shape on every rank, so the skip layer's
         # total count is the main layer's: one copy is kept, and this one is
@@ -542,6 +560,7 @@ class SyncBatchNormDualActFunction(torch.autograd.Function):
         mean, invstd, count, coefs = compute_sync_stats(
             x, eps, momentum, running_mean, running_var,
             process_group, world_size, weight, bias, want_coefs=True,
+            partials=partials, nchunks=nchunks,
         )
         # what the composition's residual, bn_skip(x_skip), would require
         need_r = any(ctx.needs_input_grad[i] for i in (1, 4, 5))
@@ -596,7 +615,7 @@ class SyncBatchNormDualActFunction(torch.autograd.Function):
         if grad_output is None:  # fork with only the second output used
             grad_output, grad_skip = grad_skip, None
         if grad_output is None:
-            return (None,) * 17
+            return (None,) * 21
         (x, x2, r, gate, weight, bias, weight2, bias2, mean, invstd, mean2,
          invstd2, count, coefs, _coefs2) = ctx.saved_tensors
         need_x, need_x2 = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
@@ -624,7 +643,7 @@ class SyncBatchNormDualActFunction(torch.autograd.Function):
                 dx if need_x else None, dx2 if need_x2 else None,
                 gw if need_w else None, gb if need_b else None,
                 gw2 if need_w2 else None, gb2 if need_b2 else None,
-            ) + (None,) * 11
+            ) + (None,) * 15
 
         # both gradients of a forked output reach the GPU reduce unsummed
         fold = grad_skip is not None and x.is_cuda and x.numel() > 0
@@ -750,8 +769,127 @@ def dual_bn_eligible(bn, bn_skip, x: torch.Tensor) -> bool:
     return True
 
 
+class Conv1x1StatsFunction(torch.autograd.Function):
+    """A 1x1 stride-1 convolution through ``ops.conv1x1_stats``: returns
+    ``(y, partials)``, ``partials`` being the fp64 ``[Cout, nchunks, 2]``
+    workspace of the following BatchNorm's statistics (not differentiable).
+    The backward is the stock convolution backward on the saved ``(x,
+    weight)``.  Callers check that the op takes the tensors
+    (``conv_stats_eligible``)."""
+
+    @staticmethod
+    def forward(ctx, x: torch.Tensor, weight: torch.Tensor):
+        y, partials, _ = ops.conv1x1_stats(x, weight)
+        if y is None:
+            raise RuntimeError("conv1x1_stats declined tensors its plan takes")
+        ctx.save_for_backward(x, weight)
+        ctx.mark_non_differentiable(partials)
+        return y, partials
+
+    @staticmethod
+    def backward(ctx, grad_y, _grad_partials=None):
+        x, weight = ctx.saved_tensors
+        mask = [ctx.needs_input_grad[0], ctx.needs_input_grad[1], False]
+        dx, dw, _ = torch.ops.aten.convolution_backward(
+            grad_y, x, weight, None, [1, 1], [0, 0], [1, 1], False, [0, 0],
+            1, mask,
+        )
+        return (dx if mask[0] else None), (dw if mask[1] else None)
+
+
+def _pair(v):
+    return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+
+
+def _takes_partials(bn) -> bool:
+    """A BatchNorm whose training forward can start from finished partial
+    sums: exactly SyncBatchNormAct2d (out of place) or SyncBatchNorm, in
+    training mode, without hooks."""
+    return (
+        (type(bn) is SyncBatchNormAct2d or type(bn) is SyncBatchNorm)
+        and bn.training and not getattr(bn, "inplace", False)
+        and not _hooked(bn)
+    )
+
+
+def conv_stats_eligible(conv, bn, x: torch.Tensor) -> bool:
+    """True when ``bn(conv(x))`` can run as conv1x1_stats + finalize: an
+    ``nn.Conv2d`` proper that is 1x1, stride 1, unpadded, undilated,
+    ungrouped, bias-free and hook-free, a BatchNorm that ``_takes_partials``,
+    autocast off, and tensors the kernel takes (``ops.conv1x1_stats``)."""
+    if not (
+        type(conv) is torch.nn.Conv2d and conv.bias is None
+        and _pair(conv.kernel_size) == (1, 1) and _pair(conv.stride) == (1, 1)
+        and _pair(conv.padding) == (0, 0) and _pair(conv.dilation) == (1, 1)
+        and conv.groups == 1 and not _hooked(conv) and _takes_partials(bn)
+        and x.is_cuda and x.dim() == 4 and not torch.is_autocast_enabled()
+    ):
+        return False
+    plan = ops.launch_plan("conv1x1_stats", x, (conv.weight,))
+    return plan["path"] == "mfma"
+
+
+def conv1x1_with_stats(conv, bn, x: torch.Tensor):
+    """``(conv(x), partials)``: through ``Conv1x1StatsFunction`` where
+    ``conv_stats_eligible``, else the module's own convolution and None."""
+    if conv_stats_eligible(conv, bn, x):
+        return Conv1x1StatsFunction.apply(x, conv.weight)
+    return conv(x), None
+
+
+def _bn_from_partials(bn, y, residual, fork, partials):
+    """``bn(y, residual=, fork=)`` for a ``_takes_partials`` module, the
+    statistics of ``y`` taken from ``partials``."""
+    bn._check_input_dim(y)
+    bn._check_non_zero_input_channels(y)
+    if bn.track_running_stats and bn.num_batches_tracked is not None:
+        bn.num_batches_tracked.add_(1)
+    process_group = None
+    world_size = 1
+    if dist.is_available() and dist.is_initialized():
+        process_group = bn.process_group or dist.group.WORLD
+        world_size = dist.get_world_size(process_group)
+    running_mean = bn.running_mean if bn.track_running_stats else None
+    running_var = bn.running_var if bn.track_running_stats else None
+    return SyncBatchNormActFunction.apply(
+        y, residual, bn.weight, bn.bias, running_mean, running_var, bn.eps,
+        _momentum_factor(bn), process_group, world_size,
+        getattr(bn, "relu", False), getattr(bn, "negative_slope", 0.0), fork,
+        getattr(bn, "gate_bits", False), partials, int(partials.shape[1]),
+    )
+
+
+def _bn_call(bn, y, residual, fork, partials=None):
+    """The single layer: from ``partials`` where there are some and the
+    module can start from them, else the module's own ``forward``."""
+    act = isinstance(bn, SyncBatchNormAct2d)
+    if partials is not None and _takes_partials(bn) and (
+            act or (residual is None and not fork)):
+        return _bn_from_partials(bn, y, residual, fork, partials)
+    kwargs = {}
+    if residual is not None:
+        kwargs["residual"] = residual
+    if fork:
+        kwargs["fork"] = True
+    return bn(y, **kwargs)
+
+
+def conv1x1_bn_act(conv, bn, x: torch.Tensor,
+                   residual: Optional[torch.Tensor] = None,
+                   fork: bool = False):
+    """``bn(conv(x), residual=residual, fork=fork)`` for a 1x1 convolution
+    and the BatchNorm after it.  Where ``conv_stats_eligible`` the
+    convolution runs as this project's MFMA kernel, which forms the
+    BatchNorm's statistics from its accumulators: the statistics pass over
+    the conv output does not run.  The output then differs from the
+    composition's by the convolution's accumulation order (both accumulate in
+    fp32 and round once).  Anything else is exactly the composition."""
+    y, partials = conv1x1_with_stats(conv, bn, x)
+    return _bn_call(bn, y, residual, fork, partials)
+
+
 def bn_add_bn_act(bn, bn_skip, x: torch.Tensor, x_skip: torch.Tensor,
-                  fork: bool = False):
+                  fork: bool = False, *, partials=None, partials_skip=None):
     """``bn(x, residual=bn_skip(x_skip), fork=fork)`` for the closing
     SyncBatchNormAct2d ``bn`` of a residual block and the SyncBatchNorm
     ``bn_skip`` of its downsample path: one dual layer where
@@ -759,7 +897,11 @@ def bn_add_bn_act(bn, bn_skip, x: torch.Tensor, x_skip: torch.Tensor,
     swapped modules, eval mode, fp32, CPU, hooks).  ``fork=True`` returns a
     ``(main, skip)`` pair (SyncBatchNormAct2d.forward).  Both modules'
     running statistics and ``num_batches_tracked`` move as their own
-    ``forward`` would move them."""
+    ``forward`` would move them.
+
+    ``partials`` / ``partials_skip``: the ``conv1x1_with_stats`` workspace
+    of ``x`` / ``x_skip`` (each optional on its own); that layer's statistics
+    are then finalized from it, on the dual route and in the composition."""
     eligible = dual_bn_eligible(bn, bn_skip, x)
     process_group = None
     world_size = 1
@@ -778,6 +920,9 @@ def bn_add_bn_act(bn, bn_skip, x: torch.Tensor, x_skip: torch.Tensor,
                                            bn_skip.running_var)
         )
     if not eligible:
+        if partials is not None or partials_skip is not None:
+            r = _bn_call(bn_skip, x_skip, None, False, partials_skip)
+            return _bn_call(bn, x, r, fork, partials)
         if fork:
             return bn(x, residual=bn_skip(x_skip), fork=True)
         return bn(x, residual=bn_skip(x_skip))
@@ -797,6 +942,9 @@ def bn_add_bn_act(bn, bn_skip, x: torch.Tensor, x_skip: torch.Tensor,
         *running(bn), *running(bn_skip), bn.eps, bn_skip.eps,
         _momentum_factor(bn), _momentum_factor(bn_skip), process_group,
         world_size, fork,
+        partials, None if partials is None else int(partials.shape[1]),
+        partials_skip,
+        None if partials_skip is None else int(partials_skip.shape[1]),
     )
 
 

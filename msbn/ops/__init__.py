@@ -505,6 +505,58 @@ def batch_norm_frozen_backward_elemt(grad_out, input, residual, coefs,
     )
 
 
+def conv1x1_stats(input: torch.Tensor, weight: torch.Tensor):
+    """A 1x1, stride-1, unpadded, ungrouped, bias-free convolution as one
+    MFMA GEMM kernel that also forms the statistics of the BatchNorm that
+    follows it (docs/KERNEL_DESIGN.md "Conv + statistics").
+
+    Returns ``(y, partials, nchunks)``: ``y`` channels-last ``[N, Cout, H,
+    W]``, accumulated in fp32 and rounded to the input dtype once;
+    ``partials`` the fp64 ``[Cout][nchunks][2]`` workspace of per-channel
+    ``{sum y, sum y^2}`` over the rounded values, which
+    ``batch_norm_stats_local_from_partials`` /
+    ``batch_norm_stats_packed_from_partials`` finalize.
+
+    Returns ``(None, None, 0)`` and launches nothing for what the kernel
+    does not take: anything but a non-empty dense channels-last 4-D bf16 /
+    half GPU input with a contiguous ``[Cout, Cin, 1, 1]`` weight of the same
+    dtype, ``Cin`` and ``Cout`` multiples of 8 (``Cin <= 2304``) and 16-byte
+    aligned pointers.  The caller then runs the convolution it has."""
+    if not input.is_cuda or not weight.is_cuda:
+        return None, None, 0
+    y, partials, nchunks = _require_hip().conv1x1_stats(input, weight)
+    if y is None:
+        return None, None, 0
+    return y, partials, int(nchunks)
+
+
+def batch_norm_stats_local_from_partials(partials, nchunks: int, count: int,
+                                         eps: float, running_mean,
+                                         running_var, momentum: float,
+                                         weight, bias, want_coefs: bool):
+    """``batch_norm_stats_local`` for statistics whose partial stage is done
+    (``conv1x1_stats``): the finalize kernel alone, with the running-stat
+    update and the ``[scale | shift]`` coefs.  ``count`` is the number of
+    elements per channel.  Returns ``(mean, invstd, count[1], coefs|None)``."""
+    mean, invstd, count_sum, coefs = (
+        _require_hip().batch_norm_stats_local_from_partials(
+            partials, nchunks, count, eps, running_mean, running_var,
+            momentum, weight, bias, want_coefs,
+        )
+    )
+    return mean, invstd, count_sum, (coefs if want_coefs else None)
+
+
+def batch_norm_stats_packed_from_partials(partials, nchunks: int, count: int,
+                                          eps: float, out: torch.Tensor):
+    """``batch_norm_stats_packed`` from finished partials: writes
+    ``[mean(C) | invstd(C) | count(1)]`` into ``out``."""
+    _require_hip().batch_norm_stats_packed_from_partials(
+        partials, nchunks, count, eps, out
+    )
+    return out
+
+
 def launch_plan(kind: str, input: torch.Tensor, others=(), coefs=None) -> dict:
     """What a GPU op WOULD launch for these tensors — host-only, launches
     nothing.  The numbers come from the same host code the ops launch with.
@@ -528,6 +580,12 @@ def launch_plan(kind: str, input: torch.Tensor, others=(), coefs=None) -> dict:
       ``"bwd_reduce_dual"``   input = x, others = (grad_out, x2, gm_out,
                                                    grad_out2, gate)
       ``"bwd_elemt_dual"``    input = x, others = (gm, x2)
+      ``"conv1x1_stats"``     input = x, others = (weight,)
+    ``conv1x1_stats`` reports path ``"mfma"`` with ``nchunks``, ``row_tile``
+    (rows of a tile), ``slab`` (output channels of a block), ``nslabs``,
+    ``tiles_per_block`` (most row tiles one block visits), ``k_trips`` and
+    ``lds_bytes``, or ``"ineligible"`` where the op declines (the device is
+    not looked at: the plan of a CPU tensor is that of its GPU copy).
     ``None`` entries of ``others`` are absent tensors.  The dual kinds
     report path ``"nhwc"`` with their single counterparts' numbers plus
     ``dual: True``, or ``"ineligible"`` where the dual kernels decline.
@@ -553,6 +611,9 @@ __all__ = [
     "hip_available",
     "launch_plan",
     "gate_bits_empty",
+    "conv1x1_stats",
+    "batch_norm_stats_local_from_partials",
+    "batch_norm_stats_packed_from_partials",
     "bn_frozen_coefs",
     "batch_norm_frozen_backward_elemt",
     "batch_norm_elemt_act_dual",

@@ -27,6 +27,7 @@
 #include <c10/hip/HIPStream.h>
 
 #include <algorithm>
+#include <climits>
 #include <map>
 #include <string>
 #include <vector>
@@ -2495,20 +2496,11 @@ hipStream_t cur_stream() {
     }                                                                       \
   }()
 
-void stats_into(const at::Tensor& input, double eps, float* mean_p,
-                float* invstd_p, float* count_p, const at::Tensor* rmean,
-                const at::Tensor* rvar, double momentum,
-                const at::Tensor* wpar = nullptr,
-                const at::Tensor* bpar = nullptr, float* scale_p = nullptr,
-                float* shift_p = nullptr) {
-  const Layout L = get_layout(input);
-  const int64_t count = L.rows;
+// Stage 1: the layout's partial kernel -> fp64 workspace [C][nchunks][2].
+at::Tensor stats_partials(const at::Tensor& input, const Layout& L,
+                          int* nchunks_out) {
   auto stream = cur_stream();
-  const auto rstat_type = rmean ? rmean->scalar_type() : at::kFloat;
-  const auto w_type = wpar ? wpar->scalar_type()
-                     : bpar ? bpar->scalar_type()
-                            : at::kFloat;
-
+  at::Tensor ws;
   MSBN_DISPATCH_FLOAT_TYPES(input.scalar_type(), "batch_norm_stats", [&] {
     const native_t* x =
         reinterpret_cast<const native_t*>(input.data_ptr<scalar_t>());
@@ -2516,8 +2508,9 @@ void stats_into(const at::Tensor& input, double eps, float* mean_p,
     const ReducePlan plan = plan_reduce(L, (int)sizeof(native_t), {x});
     const int v = plan.v;
     const int nchunks = plan.nchunks;
-    at::Tensor ws = at::empty({(int64_t)nchunks * L.C * 2},
-                              input.options().dtype(at::kDouble));
+    *nchunks_out = nchunks;
+    ws = at::empty({(int64_t)nchunks * L.C * 2},
+                   input.options().dtype(at::kDouble));
     if (plan.path == RedPath::NchwFlat) {
       const auto& g = plan.flat;
       hipLaunchKernelGGL((bn_stats_partial_nchw_flat<native_t>), g.grid,
@@ -2540,25 +2533,54 @@ void stats_into(const at::Tensor& input, double eps, float* mean_p,
                            g.lpr);
       });
     }
-    const int fgrid = (int)cdiv(L.C, kFinalizeWavesPerBlock);
-    MSBN_DISPATCH_RSTAT(rstat_type, "batch_norm_stats", [&] {
-      MSBN_DISPATCH_WTYPE(w_type, "batch_norm_stats", [&] {
-        rstat_t* rm = rmean ? reinterpret_cast<rstat_t*>(rmean->data_ptr())
-                            : nullptr;
-        rstat_t* rv = rvar ? reinterpret_cast<rstat_t*>(rvar->data_ptr())
-                           : nullptr;
-        const wt_t* wp =
-            wpar ? reinterpret_cast<const wt_t*>(wpar->data_ptr()) : nullptr;
-        const wt_t* bp =
-            bpar ? reinterpret_cast<const wt_t*>(bpar->data_ptr()) : nullptr;
-        hipLaunchKernelGGL((bn_stats_finalize<rstat_t, wt_t>), dim3(fgrid),
-                           dim3(MSBN_BLOCK), 0, stream, ws.data_ptr<double>(),
-                           nchunks, L.C, (double)count, (float)eps, mean_p,
-                           invstd_p, count_p, rm, rv, (float)momentum, wp, bp,
-                           scale_p, shift_p);
-      });
+  });
+  return ws;
+}
+
+// Stage 2: bn_stats_finalize over a workspace of `nchunks` partials per
+// channel, whoever wrote it.
+void stats_finalize(const at::Tensor& ws, int nchunks, int64_t C,
+                    int64_t count, double eps, float* mean_p, float* invstd_p,
+                    float* count_p, const at::Tensor* rmean,
+                    const at::Tensor* rvar, double momentum,
+                    const at::Tensor* wpar, const at::Tensor* bpar,
+                    float* scale_p, float* shift_p) {
+  auto stream = cur_stream();
+  const auto rstat_type = rmean ? rmean->scalar_type() : at::kFloat;
+  const auto w_type = wpar ? wpar->scalar_type()
+                     : bpar ? bpar->scalar_type()
+                            : at::kFloat;
+  const int fgrid = (int)cdiv(C, kFinalizeWavesPerBlock);
+  MSBN_DISPATCH_RSTAT(rstat_type, "batch_norm_stats", [&] {
+    MSBN_DISPATCH_WTYPE(w_type, "batch_norm_stats", [&] {
+      rstat_t* rm = rmean ? reinterpret_cast<rstat_t*>(rmean->data_ptr())
+                          : nullptr;
+      rstat_t* rv = rvar ? reinterpret_cast<rstat_t*>(rvar->data_ptr())
+                         : nullptr;
+      const wt_t* wp =
+          wpar ? reinterpret_cast<const wt_t*>(wpar->data_ptr()) : nullptr;
+      const wt_t* bp =
+          bpar ? reinterpret_cast<const wt_t*>(bpar->data_ptr()) : nullptr;
+      hipLaunchKernelGGL((bn_stats_finalize<rstat_t, wt_t>), dim3(fgrid),
+                         dim3(MSBN_BLOCK), 0, stream, ws.data_ptr<double>(),
+                         nchunks, C, (double)count, (float)eps, mean_p,
+                         invstd_p, count_p, rm, rv, (float)momentum, wp, bp,
+                         scale_p, shift_p);
     });
   });
+}
+
+void stats_into(const at::Tensor& input, double eps, float* mean_p,
+                float* invstd_p, float* count_p, const at::Tensor* rmean,
+                const at::Tensor* rvar, double momentum,
+                const at::Tensor* wpar = nullptr,
+                const at::Tensor* bpar = nullptr, float* scale_p = nullptr,
+                float* shift_p = nullptr) {
+  const Layout L = get_layout(input);
+  int nchunks = 0;
+  const at::Tensor ws = stats_partials(input, L, &nchunks);
+  stats_finalize(ws, nchunks, L.C, L.rows, eps, mean_p, invstd_p, count_p,
+                 rmean, rvar, momentum, wpar, bpar, scale_p, shift_p);
 }
 
 }  // namespace
@@ -2696,6 +2718,70 @@ batch_norm_stats_local(const at::Tensor& input, double eps,
              count_sum.data_ptr<float>(), rm, rv, momentum, wp, bp, scale_p,
              shift_p);
   return {mean, invstd, count_sum, coefs};
+}
+
+namespace {
+// C of a [C][nchunks][2] fp64 workspace, after checking that it is one
+int64_t partials_channels(const at::Tensor& partials, int64_t nchunks,
+                          int64_t count, const char* name) {
+  TORCH_CHECK(partials.defined() && partials.is_cuda() &&
+                  partials.scalar_type() == at::kDouble &&
+                  partials.is_contiguous(),
+              name, ": partials must be a contiguous fp64 GPU tensor");
+  TORCH_CHECK(nchunks > 0 && nchunks <= INT_MAX && count > 0 &&
+                  partials.numel() > 0 &&
+                  partials.numel() % (2 * nchunks) == 0,
+              name, ": partials must hold [C][nchunks][2] for a non-empty "
+                    "input");
+  return partials.numel() / (2 * nchunks);
+}
+}  // namespace
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor>
+batch_norm_stats_local_from_partials(
+    const at::Tensor& partials, int64_t nchunks, int64_t count, double eps,
+    const c10::optional<at::Tensor>& running_mean,
+    const c10::optional<at::Tensor>& running_var, double momentum,
+    const c10::optional<at::Tensor>& weight,
+    const c10::optional<at::Tensor>& bias, bool want_coefs) {
+  const int64_t C = partials_channels(partials, nchunks, count,
+                                      "batch_norm_stats_local_from_partials");
+  auto opts = partials.options().dtype(at::kFloat);
+  auto mean = at::empty({C}, opts);
+  auto invstd = at::empty({C}, opts);
+  auto count_sum = at::empty({1}, opts);
+  at::Tensor coefs;
+  float* scale_p = nullptr;
+  float* shift_p = nullptr;
+  if (want_coefs) {
+    coefs = at::empty({2 * C}, opts);
+    scale_p = coefs.data_ptr<float>();
+    shift_p = scale_p + C;
+  }
+  const at::Tensor* rm =
+      running_mean.has_value() ? &running_mean.value() : nullptr;
+  const at::Tensor* rv =
+      running_var.has_value() ? &running_var.value() : nullptr;
+  const at::Tensor* wp = weight.has_value() ? &weight.value() : nullptr;
+  const at::Tensor* bp = bias.has_value() ? &bias.value() : nullptr;
+  stats_finalize(partials, (int)nchunks, C, count, eps,
+                 mean.data_ptr<float>(), invstd.data_ptr<float>(),
+                 count_sum.data_ptr<float>(), rm, rv, momentum, wp, bp,
+                 scale_p, shift_p);
+  return {mean, invstd, count_sum, coefs};
+}
+
+void batch_norm_stats_packed_from_partials(const at::Tensor& partials,
+                                           int64_t nchunks, int64_t count,
+                                           double eps, at::Tensor& out) {
+  const int64_t C = partials_channels(partials, nchunks, count,
+                                      "batch_norm_stats_packed_from_partials");
+  TORCH_CHECK(out.is_contiguous() && out.numel() == 2 * C + 1 &&
+                  out.scalar_type() == at::kFloat,
+              "packed stats buffer must be contiguous fp32 of size 2C+1");
+  float* p = out.data_ptr<float>();
+  stats_finalize(partials, (int)nchunks, C, count, eps, p, p + C, p + 2 * C,
+                 nullptr, nullptr, 0.0, nullptr, nullptr, nullptr, nullptr);
 }
 
 std::tuple<at::Tensor, at::Tensor> batch_norm_gather_stats_with_counts(
@@ -4356,6 +4442,22 @@ std::tuple<std::string, std::map<std::string, int64_t>> launch_plan(
                           : nullptr;
   std::map<std::string, int64_t> d;
   std::string path;
+
+  // 1x1 conv + statistics: others = {weight}
+  if (kind == "conv1x1_stats") {
+    if (!given(0)) return {"ineligible", d};
+    const Conv1x1Plan p = conv1x1_plan(input, *others[0]);
+    if (!p.ok) return {"ineligible", d};
+    d["nchunks"] = p.nchunks;
+    d["row_tile"] = p.row_tile;
+    d["slab"] = p.slab;
+    d["nslabs"] = p.nslabs;
+    d["tiles_per_block"] = p.tiles_per_block;
+    d["k_trips"] = p.k_trips;
+    d["lds_bytes"] = (int64_t)p.lds_bytes;
+    d["finalize_trips"] = cdiv(p.nchunks, MSBN_WAVE);
+    return {"mfma", d};
+  }
 
   // dual BN: the single counterparts' numbers plus "dual", or "ineligible"
   // where the ops decline and the composition runs

@@ -295,6 +295,54 @@ std::tuple<at::Tensor, at::Tensor> batch_norm_backward_elemt_dual(
     const c10::optional<at::Tensor>& weight2, const at::Tensor& sums,
     const at::Tensor& count);
 
+// ---- 1x1 conv + statistics (conv_stats_kernels.hip) ------------------------
+// A 1x1, stride-1, unpadded, ungrouped, bias-free convolution of a dense
+// channels-last 4-D bf16 / half input, run as one MFMA GEMM kernel that also
+// forms the per-channel {sum y, sum y^2} of the output it stores (fp32
+// accumulation, rounded to the input dtype once; the statistics are those of
+// the rounded values).  Returns (y, partials, nchunks): y channels-last
+// [N, Cout, H, W]; partials the fp64 workspace [Cout][nchunks][2] that the
+// *_from_partials ops below finalize.
+//
+// Declines -- (undefined, undefined, 0), nothing launched -- for anything
+// else: a CPU, fp32, empty or not dense channels-last input, a weight of
+// another dtype / device / shape or not contiguous, Cin or Cout not a
+// multiple of 8, a pointer off 16-byte alignment, and a Cin whose 32-column
+// weight slab does not fit the LDS (Cin > 2304).
+std::tuple<at::Tensor, at::Tensor, int64_t> conv1x1_stats(
+    const at::Tensor& input, const at::Tensor& weight);
+
+// The launch conv1x1_stats would make (device not considered); ok == false
+// where it declines.
+struct Conv1x1Plan {
+  bool ok;
+  int64_t rows, cin, cout;
+  int row_tile;         // rows of a tile
+  int slab;             // output channels of a block
+  int nslabs;           // grid.x
+  int nchunks;          // grid.y: row runs = partials per channel
+  int tiles_per_block;  // most row tiles one block visits
+  int k_trips;          // 128-element trips of the K loop
+  size_t lds_bytes;
+};
+Conv1x1Plan conv1x1_plan(const at::Tensor& input, const at::Tensor& weight);
+
+// batch_norm_stats_local / batch_norm_stats_packed with the partial stage
+// already done: they run bn_stats_finalize alone over `partials`
+// (fp64 [C][nchunks][2] of {sum x, sum x^2}, `count` elements per channel)
+// and give their siblings' outputs, running-stat update and coefs.
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor>
+batch_norm_stats_local_from_partials(
+    const at::Tensor& partials, int64_t nchunks, int64_t count, double eps,
+    const c10::optional<at::Tensor>& running_mean,
+    const c10::optional<at::Tensor>& running_var, double momentum,
+    const c10::optional<at::Tensor>& weight,
+    const c10::optional<at::Tensor>& bias, bool want_coefs);
+
+void batch_norm_stats_packed_from_partials(const at::Tensor& partials,
+                                           int64_t nchunks, int64_t count,
+                                           double eps, at::Tensor& out);
+
 // ---- launch plan (host only, launches nothing) ----------------------------
 // Which kernel path a call would take and how far its loops run, decided by
 // the same host code the ops launch with.  kind / tensors:
@@ -316,6 +364,9 @@ std::tuple<at::Tensor, at::Tensor> batch_norm_backward_elemt_dual(
 //   "bwd_reduce_dual"    input = x,      others = {grad_out, x2, gm_out,
 //                                                  grad_out2, gate}
 //   "bwd_elemt_dual"     input = x,      others = {gm, x2}
+//   "conv1x1_stats"      input = x,      others = {weight}: path "mfma" with
+//                        nchunks, row_tile, slab, nslabs, tiles_per_block,
+//                        k_trips and lds_bytes, or "ineligible"
 // (pass only what the op itself would dereference).  Returns (path, numbers):
 // path is "nchw_vec" | "nchw_flat" | "nhwc" | "small_plane" | "ineligible";
 // the dual kinds report "nhwc" with their single counterparts' numbers plus

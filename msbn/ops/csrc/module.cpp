@@ -118,6 +118,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("weight"), py::arg("weight2"), py::arg("sums"),
         py::arg("count"));
 
+  m.def("conv1x1_stats", &msbn::conv1x1_stats, py::arg("input"),
+        py::arg("weight"));
+  m.def("batch_norm_stats_local_from_partials",
+        &msbn::batch_norm_stats_local_from_partials, py::arg("partials"),
+        py::arg("nchunks"), py::arg("count"), py::arg("eps"),
+        py::arg("running_mean"), py::arg("running_var"), py::arg("momentum"),
+        py::arg("weight"), py::arg("bias"), py::arg("want_coefs"));
+  m.def("batch_norm_stats_packed_from_partials",
+        &msbn::batch_norm_stats_packed_from_partials, py::arg("partials"),
+        py::arg("nchunks"), py::arg("count"), py::arg("eps"), py::arg("out"));
+
   m.def("bn_frozen_coefs", &msbn::bn_frozen_coefs, py::arg("running_mean"),
         py::arg("running_var"), py::arg("eps"), py::arg("weight"),
         py::arg("bias"));

@@ -21,6 +21,7 @@ ext = CUDAExtension(
     sources=[
         os.path.join(CSRC, "module.cpp"),
         os.path.join(CSRC, "bn_kernels.hip"),
+        os.path.join(CSRC, "conv_stats_kernels.hip"),
     ],
     include_dirs=[CSRC],
     extra_compile_args={
@@ -40,6 +41,7 @@ if os.environ.get("MSBN_BUILD_NONT", "0") == "1":
         sources=[
             os.path.join(CSRC, "module_nont_ab.cpp"),
             os.path.join(CSRC, "bn_kernels_nont_ab.hip"),
+            os.path.join(CSRC, "conv_stats_kernels_nont_ab.hip"),
         ],
         include_dirs=[CSRC],
         extra_compile_args={
