@@ -53,6 +53,11 @@ def main():
                    help="build the backbone with the fused BN(+add)+ReLU "
                         "epilogues (msbn only; --stock has no fused modules "
                         "and keeps the unfused backbone)")
+    p.add_argument("--grouped-heads", action="store_true",
+                   help="run each head BatchNorm+ReLU over the five pyramid "
+                        "levels as one grouped layer (msbn only; the grouped "
+                        "kernels take channels-last, so NCHW runs keep the "
+                        "per-level loop)")
     p.add_argument("--local_rank", "--local-rank", type=int,
                    default=int(os.environ.get("LOCAL_RANK", 0)),
                    dest="local_rank")
@@ -104,7 +109,8 @@ def main():
     else:
         model = msbn.convert_sync_batchnorm(msbn.models.retinanet(
             frozen_backbone=args.frozen_backbone,
-            fused_backbone=args.fused_backbone)).to(device)
+            fused_backbone=args.fused_backbone,
+            grouped_heads=args.grouped_heads)).to(device)
     dtype = torch.bfloat16 if (args.dtype == "bf16" and use_cuda) else \
         torch.float32
     if dtype == torch.bfloat16:
@@ -207,6 +213,8 @@ def main():
                        else "contiguous",
                        "frozen_backbone": args.frozen_backbone,
                        "fused_backbone": args.fused_backbone
+                       and not args.stock,
+                       "grouped_heads": args.grouped_heads
                        and not args.stock,
                        "impl": "stock" if args.stock else "msbn"},
         }))

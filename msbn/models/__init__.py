@@ -16,13 +16,16 @@ __all__ = [
 
 
 def retinanet(num_classes: int = 80, frozen_backbone: bool = False,
-              fused_backbone: bool = False):
+              fused_backbone: bool = False, grouped_heads: bool = False):
     """RetinaNet-R50-FPN.  ``fused_backbone`` builds the backbone with the
     fused BN(+add)+ReLU epilogues; ``frozen_backbone`` freezes every backbone
     BatchNorm (the detection fine-tuning recipe) — the heads keep trainable,
-    sync-able BN.  The defaults give the plain trainable model."""
+    sync-able BN; ``grouped_heads`` runs each head BatchNorm+ReLU over the
+    five pyramid levels as one grouped layer.  The defaults give the plain
+    trainable model."""
     return RetinaNet(num_classes, frozen_backbone=frozen_backbone,
-                     fused_backbone=fused_backbone)
+                     fused_backbone=fused_backbone,
+                     grouped_heads=grouped_heads)
 
 
 def convert_to_torch_batchnorm(module):

@@ -46,10 +46,21 @@ class FPN(nn.Module):
 
 
 class Head(nn.Module):
-    """Shared 4-conv head with BN (detection heads are where SyncBN pays)."""
+    """Shared 4-conv head with BN (detection heads are where SyncBN pays).
 
-    def __init__(self, in_channels: int, out_per_anchor: int, num_anchors: int = 9):
+    ``grouped=True``: ``forward`` takes the LIST of pyramid levels and runs
+    layer-major -- each tower convolution on every level, then one grouped
+    BatchNorm+ReLU over the levels (``msbn.nn.fused.bn_act_grouped``: one
+    set of launches and one collective each way per tower layer, where the
+    level-major order issues one per level) -- and returns the list of
+    predictions.  Same modules, names and ``state_dict`` keys; each level is
+    still normalised with its own batch statistics and the running
+    statistics see the levels in the same order."""
+
+    def __init__(self, in_channels: int, out_per_anchor: int,
+                 num_anchors: int = 9, grouped: bool = False):
         super().__init__()
+        self.grouped = grouped
         layers = []
         for _ in range(4):
             layers += [
@@ -63,13 +74,22 @@ class Head(nn.Module):
         self.out_per_anchor = out_per_anchor
 
     def forward(self, x):
-        return self.pred(self.tower(x))
+        if not self.grouped:
+            return self.pred(self.tower(x))
+        from msbn.nn.fused import bn_act_grouped
+
+        feats = list(x)
+        for i in range(0, len(self.tower), 3):
+            conv, bn = self.tower[i], self.tower[i + 1]
+            feats = bn_act_grouped(bn, [conv(f) for f in feats], relu=True)
+        return [self.pred(f) for f in feats]
 
 
 class RetinaNet(nn.Module):
     def __init__(self, num_classes: int = 80, frozen_backbone: bool = False,
-                 fused_backbone: bool = False):
+                 fused_backbone: bool = False, grouped_heads: bool = False):
         super().__init__()
+        self.grouped_heads = grouped_heads
         self.backbone = resnet50(fused=True) if fused_backbone else resnet50()
         del self.backbone.fc, self.backbone.avgpool
         if frozen_backbone:
@@ -79,8 +99,8 @@ class RetinaNet(nn.Module):
 
             self.backbone = freeze_batchnorm(self.backbone)
         self.fpn = FPN([512, 1024, 2048], 256)
-        self.cls_head = Head(256, num_classes)
-        self.box_head = Head(256, 4)
+        self.cls_head = Head(256, num_classes, grouped=grouped_heads)
+        self.box_head = Head(256, 4, grouped=grouped_heads)
         self.num_classes = num_classes
         # focal-style bias init on the classification logits
         nn.init.constant_(self.cls_head.pred.bias, -math.log((1 - 0.01) / 0.01))
@@ -88,6 +108,8 @@ class RetinaNet(nn.Module):
     def forward(self, images):
         _, c3, c4, c5 = self.backbone.forward_features(images)
         feats = self.fpn((c3, c4, c5))
+        if self.grouped_heads:
+            return self.cls_head(feats), self.box_head(feats)
         cls_outs = [self.cls_head(f) for f in feats]
         box_outs = [self.box_head(f) for f in feats]
         return cls_outs, box_outs

@@ -948,6 +948,211 @@ def bn_add_bn_act(bn, bn_skip, x: torch.Tensor, x_skip: torch.Tensor,
     )
 
 
+def _dense_aligned(t: torch.Tensor) -> torch.Tensor:
+    """``t`` as the grouped kernels read it: dense channels-last on a
+    16-byte boundary; a fresh copy where it is not."""
+    if t.numel() == 0 or (
+            t.is_contiguous(memory_format=torch.channels_last)
+            and t.data_ptr() % 16 == 0):
+        return t
+    return torch.empty_like(t, memory_format=torch.channels_last).copy_(t)
+
+
+class SyncBatchNormGroupedActFunction(torch.autograd.Function):
+    """One BatchNorm (+ReLU) over S tensors, each normalised with its own
+    batch statistics (docs/KERNEL_DESIGN.md "Grouped BN"): the levels of a
+    feature pyramid under a shared head.  Equal to S calls of the module in
+    segment order, running statistics included, at three launches forward
+    and three backward whatever S is, and with ONE all_gather of
+    ``[S, 2C+1]`` forward and ONE all_reduce of ``[S, 2C]`` backward where S
+    calls issue S of each.
+
+    The collective schedule differs from the loop's, so every rank of a
+    group must be on the same route: ``bn_act_grouped`` chooses it from
+    properties that are equal on all ranks.  A rank whose segments are all
+    empty (the ``join()`` shadow step) launches none of the kernels,
+    contributes zero counts and zero sums, and posts the same two
+    collectives."""
+
+    @staticmethod
+    def forward(ctx, weight, bias, running_mean, running_var, eps: float,
+                momentum: float, process_group, world_size: int, relu: bool,
+                *xs):
+        weight = None if weight is None else weight.contiguous()
+        bias = None if bias is None else bias.contiguous()
+        use_sync = world_size > 1 or (
+            process_group is not None and _force_sync()
+        )
+        S, C = len(xs), int(xs[0].shape[1])
+        if use_sync:
+            device = xs[0].device
+            packed = torch.empty((S, 2 * C + 1), dtype=torch.float32,
+                                 device=device)
+            ops.batch_norm_stats_packed_grouped(xs, eps, packed)
+            packed_all = torch.empty((world_size, S, 2 * C + 1),
+                                     dtype=torch.float32, device=device)
+            from msbn.nn.functions import _is_nccl_like
+            from msbn.utils import debug as _dbg
+            from msbn.utils.logging import comm_log
+            if _dbg.enabled():
+                _dbg.verify_collective("syncbn.fwd.all_gather", packed,
+                                       process_group)
+            if _is_nccl_like(process_group):
+                dist.all_gather_into_tensor(packed_all, packed,
+                                            group=process_group)
+            else:
+                chunks = list(packed_all.unbind(0))
+                dist.all_gather(chunks, packed, group=process_group)
+                packed_all = torch.stack(chunks, dim=0)
+            comm_log.record("all_gather", packed.numel() * 4,
+                            f"syncbn grouped S={S} C={C}")
+            mean, invstd, count, coefs = (
+                ops.batch_norm_gather_stats_packed_grouped(
+                    packed_all, running_mean, running_var, momentum, eps,
+                    weight, bias,
+                )
+            )
+        else:
+            mean, invstd, count, coefs = ops.batch_norm_stats_local_grouped(
+                xs, eps, running_mean, running_var, momentum, weight, bias
+            )
+        ys = ops.batch_norm_elemt_act_grouped(xs, coefs, relu)
+        ctx.save_for_backward(weight, bias, mean, invstd, count, coefs, *xs)
+        ctx.relu = relu
+        ctx.use_sync = use_sync
+        ctx.process_group = process_group
+        return tuple(ys)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        weight, bias, mean, invstd, count, coefs, *xs = ctx.saved_tensors
+        S, C = len(xs), int(xs[0].shape[1])
+        need_x = any(ctx.needs_input_grad[9:])
+        need_w = weight is not None and ctx.needs_input_grad[0]
+        need_b = bias is not None and ctx.needs_input_grad[1]
+        gos = [_dense_aligned(_match_layout(g, x)) for g, x in zip(grads, xs)]
+        if all(x.numel() == 0 for x in xs):
+            # empty-input rank (join): contribute zeros, keep peers unblocked
+            sums = torch.zeros((S, 2 * C), dtype=torch.float32,
+                               device=xs[0].device)
+            gw = torch.zeros_like(weight) if need_w else None
+            gb = torch.zeros_like(bias) if need_b else None
+        else:
+            sums, gw, gb = ops.batch_norm_backward_reduce_act_grouped(
+                gos, xs, mean, invstd, coefs, ctx.relu, need_w, need_b
+            )
+        dxs = (None,) * S
+        if need_x:
+            if ctx.use_sync:
+                from msbn.utils import debug as _dbg
+                if _dbg.enabled():  # peers verify; skipping would hang them
+                    _dbg.verify_collective("syncbn.bwd.all_reduce", sums,
+                                           ctx.process_group)
+                dist.all_reduce(sums, dist.ReduceOp.SUM,
+                                group=ctx.process_group)
+                from msbn.utils.logging import comm_log
+                comm_log.record("all_reduce", sums.numel() * 4,
+                                f"syncbn bwd grouped S={S} C={C}")
+            dxs = ops.batch_norm_backward_elemt_act_grouped(
+                gos, xs, mean, invstd, coefs, sums, count, ctx.relu
+            )
+            dxs = tuple(dx if need else None
+                        for dx, need in zip(dxs, ctx.needs_input_grad[9:]))
+        return (gw, gb, None, None, None, None, None, None, None, *dxs)
+
+
+_GROUPED_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
+
+
+def _grouped_route(bn, xs, relu: bool) -> bool:
+    """Whether ``bn_act_grouped`` takes the grouped kernels, from what is
+    equal on every rank of a group by construction: the module's type and
+    configuration (a training-mode out-of-place SyncBatchNorm,
+    SyncBatchNormAct2d without a slope, or a non-sync msbn BatchNorm; a float
+    momentum; fp32 parameters and running statistics; no hooks), S, C, the
+    dtype, the dimensionality and the device type.  Never a size."""
+    from msbn.nn.batchnorm import _BatchNorm
+
+    if not (
+        (type(bn) is SyncBatchNorm or isinstance(bn, _BatchNorm)
+         or (type(bn) is SyncBatchNormAct2d
+             and not getattr(bn, "inplace", False)
+             and getattr(bn, "negative_slope", 0.0) == 0.0
+             and relu == bn.relu))
+        and bn.training and not _hooked(bn)
+        and isinstance(bn.momentum, float)
+        and all(t is None or t.dtype == torch.float32
+                for t in (bn.weight, bn.bias, bn.running_mean,
+                          bn.running_var))
+        and 1 <= len(xs) <= 8 and not torch.is_autocast_enabled()
+    ):
+        return False
+    x0 = xs[0]
+    return (
+        x0.dtype in _GROUPED_DTYPES
+        and x0.shape[1] % (16 // x0.element_size()) == 0
+        and all(x.is_cuda and x.dim() == 4 and x.dtype == x0.dtype
+                and x.shape[1] == x0.shape[1] and x.device == x0.device
+                for x in xs)
+    )
+
+
+def bn_act_grouped(bn, xs, relu: Optional[bool] = None):
+    """``[bn(x) for x in xs]`` -- one BatchNorm module applied to S tensors
+    that share C and dtype, each normalised with its own batch statistics --
+    as one grouped layer (SyncBatchNormGroupedActFunction) where the grouped
+    kernels serve it, and exactly that loop otherwise.  Returns a list.
+
+    ``bn`` is a SyncBatchNorm, a SyncBatchNormAct2d (ReLU or no activation)
+    or a non-sync msbn BatchNorm.  ``relu=None`` applies the module's own
+    activation; ``relu=True`` on a module without one folds the ReLU that
+    follows it into the layer (the loop then runs ``torch.relu`` after the
+    module).  The running statistics move as S calls in list order move
+    them and ``num_batches_tracked`` advances by S.
+
+    Grouped: training mode, a float momentum, fp32 parameters, 1 <= S <= 8
+    dense channels-last 4-D GPU tensors (fp32 / bf16 / half) with C a
+    multiple of the 16-byte pack.  Everything else -- a residual or fork, an
+    in-place or LeakyReLU module, NCHW, ``momentum=None``, S > 8, CPU
+    tensors -- runs the loop.  With collectives in play the route is chosen
+    from rank-equal properties only (``_grouped_route``); a tensor that is
+    then not dense channels-last on a 16-byte boundary is copied, never
+    looped, so the ranks cannot part ways.  Without collectives such a group
+    runs the loop, bit for bit."""
+    xs = list(xs)
+    own = bool(getattr(bn, "relu", False))
+    relu = own if relu is None else bool(relu)
+    if own and not relu:
+        raise ValueError("relu=False cannot undo the module's own activation")
+
+    def loop():
+        ys = [bn(x) for x in xs]
+        return ys if relu == own else [torch.relu(y) for y in ys]
+
+    if not xs or not _grouped_route(bn, xs, relu):
+        return loop()
+    process_group = None
+    world_size = 1
+    if (isinstance(bn, SyncBatchNorm) and dist.is_available()
+            and dist.is_initialized()):
+        process_group = bn.process_group or dist.group.WORLD
+        world_size = dist.get_world_size(process_group)
+    if world_size > 1 or (process_group is not None and _force_sync()):
+        xs = [_dense_aligned(x) for x in xs]
+    elif ops.launch_plan("stats_grouped", xs[0], xs[1:])["path"] != "nhwc":
+        return loop()
+    for x in xs:
+        bn._check_input_dim(x)
+    if bn.track_running_stats and bn.num_batches_tracked is not None:
+        bn.num_batches_tracked.add_(len(xs))
+    running_mean = bn.running_mean if bn.track_running_stats else None
+    running_var = bn.running_var if bn.track_running_stats else None
+    return list(SyncBatchNormGroupedActFunction.apply(
+        bn.weight, bn.bias, running_mean, running_var, bn.eps, bn.momentum,
+        process_group, world_size, relu, *xs,
+    ))
+
+
 class InPlaceSyncBatchNormActFunction(torch.autograd.Function):
     """In-Place Activated SyncBatchNorm (Rota Bulo et al., 2018): the output
     ``y = act(bn(x))`` is written over ``x`` and the backward works from ``y``

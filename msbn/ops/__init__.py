@@ -557,6 +557,84 @@ def batch_norm_stats_packed_from_partials(partials, nchunks: int, count: int,
     return out
 
 
+def batch_norm_stats_local_grouped(inputs, eps: float, running_mean,
+                                   running_var, momentum: float, weight,
+                                   bias):
+    """Grouped BN (docs/KERNEL_DESIGN.md "Grouped BN"): the training
+    statistics of S tensors that share one BatchNorm, each tensor
+    ("segment") with its own, in one partial and one finalize launch.
+
+    Returns ``(mean[S, C], invstd[S, C], count[S], coefs[S, 2C])``, ``coefs``
+    holding each segment's ``[scale | shift]``.  The running statistics
+    receive S successive momentum updates in segment order, each with that
+    segment's unbiased variance: what S module calls leave.
+
+    GPU only, and only what ``launch_plan("stats_grouped", ...)`` does not
+    call ``"ineligible"``; weight, bias and running statistics fp32 or None."""
+    return _require_hip().batch_norm_stats_local_grouped(
+        list(inputs), eps, running_mean, running_var, momentum, weight, bias
+    )
+
+
+def batch_norm_stats_packed_grouped(inputs, eps: float, out: torch.Tensor):
+    """The group's message for ONE all_gather: per segment ``[mean(C) |
+    invstd(C) | count(1)]`` written into ``out`` (fp32 ``[S, 2C+1]``).  A
+    group whose segments are all empty zero-fills ``out`` without a kernel
+    of this project's."""
+    _require_hip().batch_norm_stats_packed_grouped(list(inputs), eps, out)
+    return out
+
+
+def batch_norm_gather_stats_packed_grouped(packed_all, running_mean,
+                                           running_var, momentum: float,
+                                           eps: float, weight, bias):
+    """Combine ``packed_all[world, S, 2C+1]`` per segment (count-weighted,
+    zero-count ranks masked in the kernel), apply the S running updates in
+    segment order and emit the coefs; returns what
+    ``batch_norm_stats_local_grouped`` returns."""
+    return _require_hip().batch_norm_gather_stats_packed_grouped(
+        packed_all, running_mean, running_var, momentum, eps, weight, bias
+    )
+
+
+def batch_norm_elemt_act_grouped(inputs, coefs, relu: bool):
+    """``[act(x_s * scale_s + shift_s) for s]`` in one launch; ``act`` is
+    ReLU or the identity.  The outputs are views of one allocation."""
+    return _require_hip().batch_norm_elemt_act_grouped(
+        list(inputs), coefs, relu
+    )
+
+
+def batch_norm_backward_reduce_act_grouped(grad_outs, inputs, mean, invstd,
+                                           coefs, relu: bool, weight_g: bool,
+                                           bias_g: bool):
+    """First backward pass of the group, one partial and one finalize
+    launch: ``(sums[S, 2C], grad_weight[C] | None, grad_bias[C] | None)``
+    with ``sums[s] = [sum_dy | sum_dy_xmu]`` of segment s (the buffer of the
+    group's one all_reduce) and the affine gradients summed over the
+    segments in ascending order.  The ReLU gate is recomputed from the
+    inputs and ``coefs``."""
+    sums, gw, gb = _require_hip().batch_norm_backward_reduce_act_grouped(
+        list(grad_outs), list(inputs), mean, invstd, coefs, relu, weight_g,
+        bias_g,
+    )
+    return sums, (gw if weight_g else None), (gb if bias_g else None)
+
+
+def batch_norm_backward_elemt_act_grouped(grad_outs, inputs, mean, invstd,
+                                          coefs, sums, count, relu: bool):
+    """Second backward pass of the group in one launch: ``[dx_s]`` from
+    ``sums[s]`` (summed over the ranks) and the total ``count[s]``."""
+    return _require_hip().batch_norm_backward_elemt_act_grouped(
+        list(grad_outs), list(inputs), mean, invstd, coefs, sums, count,
+        relu,
+    )
+
+
+_GROUPED_KINDS = ("stats_grouped", "elemt_grouped", "bwd_reduce_grouped",
+                  "bwd_elemt_grouped")
+
+
 def launch_plan(kind: str, input: torch.Tensor, others=(), coefs=None) -> dict:
     """What a GPU op WOULD launch for these tensors — host-only, launches
     nothing.  The numbers come from the same host code the ops launch with.
@@ -590,6 +668,21 @@ def launch_plan(kind: str, input: torch.Tensor, others=(), coefs=None) -> dict:
     report path ``"nhwc"`` with their single counterparts' numbers plus
     ``dual: True``, or ``"ineligible"`` where the dual kernels decline.
 
+    Grouped BN, ``input`` the first segment and ``others`` the rest:
+      ``"stats_grouped"``       input = x_0, others = (x_1, .., x_{S-1})
+      ``"elemt_grouped"``       the same
+      ``"bwd_reduce_grouped"``  others = (x_1, .., x_{S-1}, dy_0, .., dy_{S-1})
+      ``"bwd_elemt_grouped"``   the same
+    They report path ``"nhwc"`` with ``S`` and ``V``, or ``"ineligible"``
+    where the grouped ops decline (S > 8, another layout, C not a multiple
+    of the 16-byte pack, a pointer off 16-byte alignment, mixed dtypes or
+    channel counts; the device is not looked at).  The reduction kinds add
+    the group's ``chunk_rows``, ``lpr``, ``ctiles``, ``total_chunks``,
+    ``trips``, ``flush_every``, ``finalize_trips`` and per segment the lists
+    ``nchunks`` and ``first_block``; the elementwise kinds ``grid``,
+    ``packs``, ``trips``, ``multi_trip`` and the lists ``blocks`` and
+    ``first_block``.
+
     Returns a dict with ``path`` (``"nchw_vec"``, ``"nchw_flat"``, ``"nhwc"``,
     ``"small_plane"``, or ``"ineligible"`` for ``fused_local``), ``V`` and
     ``trips`` (the most loop iterations any one thread makes); reductions add
@@ -601,6 +694,12 @@ def launch_plan(kind: str, input: torch.Tensor, others=(), coefs=None) -> dict:
     path, numbers = _require_hip().launch_plan(kind, input, list(others), coefs)
     plan = dict(numbers)
     plan["path"] = path
+    if kind in _GROUPED_KINDS and path != "ineligible":
+        # per-segment numbers arrive as name_<s>: fold them into lists
+        for name in ("nchunks", "first_block", "blocks"):
+            if f"{name}_0" in plan:
+                plan[name] = [plan.pop(f"{name}_{s}")
+                              for s in range(plan["S"])]
     for flag in ("multi_trip", "gate", "dual"):
         if flag in plan:
             plan[flag] = bool(plan[flag])
@@ -614,6 +713,12 @@ __all__ = [
     "conv1x1_stats",
     "batch_norm_stats_local_from_partials",
     "batch_norm_stats_packed_from_partials",
+    "batch_norm_stats_local_grouped",
+    "batch_norm_stats_packed_grouped",
+    "batch_norm_gather_stats_packed_grouped",
+    "batch_norm_elemt_act_grouped",
+    "batch_norm_backward_reduce_act_grouped",
+    "batch_norm_backward_elemt_act_grouped",
     "bn_frozen_coefs",
     "batch_norm_frozen_backward_elemt",
     "batch_norm_elemt_act_dual",

@@ -22,6 +22,7 @@
 //    capped grid, fused multiply-add form).
 #include "bn_ops.hpp"
 #include "common.hpp"
+#include "launch_common.hpp"
 
 #include <ATen/ATen.h>
 #include <c10/hip/HIPStream.h>
@@ -2252,7 +2253,6 @@ int pick_v(int esize, c10::ArrayRef<const void*> ptrs, int64_t inner) {
   return 1;
 }
 
-constexpr int kTargetBlocks = 2048;  // 256 CUs x 8 blocks (guide G11)
 
 struct NchwGrid {
   dim3 grid;
@@ -2287,27 +2287,8 @@ struct NhwcGrid {
 
 NhwcGrid nhwc_grid(int64_t rows, int64_t C, int V) {
   NhwcGrid g{};
-  const int64_t cv = cdiv(C, V);
-  // Workspace traffic is C * nchunks * 16 B, written by the partial kernel
-  // and read back by finalize.  The old lpr = min(cv, 256) choice made
-  // ctiles = 1 for C >= 2048 (bf16), forcing nchunks ~ kTargetBlocks and a
-  // workspace up to HALF the payload (measured 1.4 TB/s effective at
-  // 512x2048x7x7 vs 6.3 TB/s ceiling).  Tile CHANNELS instead: pick lpr so
-  // ~16 channel tiles exist, which caps nchunks near kTargetBlocks/16 and
-  // keeps the workspace at a few % of the payload.  Lower bound lpr at 8
-  // lanes so each row segment stays >= 128 B (one full memory granule).
-  int64_t lpr = cdiv(cv, 16);
-  // round up to a power of two that divides the block
-  int64_t p2 = 8;
-  while (p2 < lpr) p2 <<= 1;
-  lpr = std::min<int64_t>(std::max<int64_t>(p2, 8), MSBN_BLOCK);
-  lpr = std::min(lpr, [&] {  // never exceed what C needs
-    int64_t q = 8;
-    while (q < cv) q <<= 1;
-    return std::min<int64_t>(q, MSBN_BLOCK);
-  }());
-  g.lpr = (int)lpr;
-  const int64_t ctiles = cdiv(C, lpr * V);
+  g.lpr = nhwc_lanes_per_row(C, V);
+  const int64_t ctiles = cdiv(C, (int64_t)g.lpr * V);
   const int64_t per_tile =
       std::max<int64_t>(1, kTargetBlocks / std::max<int64_t>(ctiles, 1));
   const int rpi = MSBN_BLOCK / g.lpr;
@@ -2584,6 +2565,30 @@ void stats_into(const at::Tensor& input, double eps, float* mean_p,
 }
 
 }  // namespace
+
+// launch_common.hpp (shared with grouped_bn_kernels.hip)
+int nhwc_lanes_per_row(int64_t C, int V) {
+  const int64_t cv = cdiv(C, V);
+  // Workspace traffic is C * nchunks * 16 B, written by the partial kernel
+  // and read back by finalize.  The old lpr = min(cv, 256) choice made
+  // ctiles = 1 for C >= 2048 (bf16), forcing nchunks ~ kTargetBlocks and a
+  // workspace up to HALF the payload (measured 1.4 TB/s effective at
+  // 512x2048x7x7 vs 6.3 TB/s ceiling).  Tile CHANNELS instead: pick lpr so
+  // ~16 channel tiles exist, which caps nchunks near kTargetBlocks/16 and
+  // keeps the workspace at a few % of the payload.  Lower bound lpr at 8
+  // lanes so each row segment stays >= 128 B (one full memory granule).
+  int64_t lpr = cdiv(cv, 16);
+  // round up to a power of two that divides the block
+  int64_t p2 = 8;
+  while (p2 < lpr) p2 <<= 1;
+  lpr = std::min<int64_t>(std::max<int64_t>(p2, 8), MSBN_BLOCK);
+  lpr = std::min(lpr, [&] {  // never exceed what C needs
+    int64_t q = 8;
+    while (q < cv) q <<= 1;
+    return std::min<int64_t>(q, MSBN_BLOCK);
+  }());
+  return (int)lpr;
+}
 
 // =====================================================================
 // public ops
@@ -4422,6 +4427,10 @@ std::tuple<std::string, std::map<std::string, int64_t>> launch_plan(
     const std::string& kind, const at::Tensor& input,
     const std::vector<c10::optional<at::Tensor>>& others,
     const c10::optional<at::Tensor>& coefs) {
+  // grouped BN: input is the first segment, others the rest
+  if (kind == "stats_grouped" || kind == "elemt_grouped" ||
+      kind == "bwd_reduce_grouped" || kind == "bwd_elemt_grouped")
+    return launch_plan_grouped(kind, input, others);
   TORCH_CHECK(input.dim() >= 2 && input.numel() > 0,
               "launch_plan: input must be a non-empty >= 2-D tensor");
   const int esize = (int)input.element_size();

@@ -343,6 +343,73 @@ void batch_norm_stats_packed_from_partials(const at::Tensor& partials,
                                            int64_t nchunks, int64_t count,
                                            double eps, at::Tensor& out);
 
+// ---- grouped BN (grouped_bn_kernels.hip) -----------------------------------
+// One training BatchNorm applied to S tensors ("segments": the levels of a
+// feature pyramid under a shared head), each normalised with its own batch
+// statistics, at a launch count that does not depend on S
+// (docs/KERNEL_DESIGN.md "Grouped BN").  Served: 1 <= S <= 8 dense
+// channels-last 4-D GPU tensors of one dtype (fp32 / bf16 / half) and one C,
+// C a multiple of the 16-byte pack (8, or 4 for fp32), 16-byte aligned
+// pointers, fp32 (or absent) weight / bias / running statistics.  Everything
+// else is an error here: callers ask launch_plan first.  A segment may be
+// empty; a group whose segments are all empty launches nothing.
+//
+// (mean[S,C], invstd[S,C], count[S], coefs[S,2C] = per segment
+// [scale | shift]); the running statistics receive S successive momentum
+// updates in segment order, each with that segment's unbiased variance.
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor>
+batch_norm_stats_local_grouped(const std::vector<at::Tensor>& inputs,
+                               double eps,
+                               const c10::optional<at::Tensor>& running_mean,
+                               const c10::optional<at::Tensor>& running_var,
+                               double momentum,
+                               const c10::optional<at::Tensor>& weight,
+                               const c10::optional<at::Tensor>& bias);
+
+// out: fp32 [S, 2C+1], per segment [mean | invstd | count]: the message of
+// ONE all_gather for the group.
+void batch_norm_stats_packed_grouped(const std::vector<at::Tensor>& inputs,
+                                     double eps, at::Tensor& out);
+
+// packed_all: [W, S, 2C+1].  Count-weighted combine per segment (zero-count
+// ranks masked in-kernel), the sequential running update, the coefs.
+// Returns what batch_norm_stats_local_grouped returns.
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor>
+batch_norm_gather_stats_packed_grouped(
+    const at::Tensor& packed_all, const c10::optional<at::Tensor>& running_mean,
+    const c10::optional<at::Tensor>& running_var, double momentum, double eps,
+    const c10::optional<at::Tensor>& weight,
+    const c10::optional<at::Tensor>& bias);
+
+// y_s = act(scale_s * x_s + shift_s), act = ReLU or none; the outputs are
+// views of one allocation.
+std::vector<at::Tensor> batch_norm_elemt_act_grouped(
+    const std::vector<at::Tensor>& inputs, const at::Tensor& coefs, bool relu);
+
+// (sums[S,2C] = per segment [sum_dy | sum_dy_xmu], grad_weight[C],
+// grad_bias[C]); the ReLU gate is recomputed from x and coefs.  grad_weight
+// / grad_bias are summed over the segments in ascending order (undefined
+// where not asked for).
+std::tuple<at::Tensor, at::Tensor, at::Tensor>
+batch_norm_backward_reduce_act_grouped(
+    const std::vector<at::Tensor>& grad_outs,
+    const std::vector<at::Tensor>& inputs, const at::Tensor& mean,
+    const at::Tensor& invstd, const at::Tensor& coefs, bool relu,
+    bool weight_g, bool bias_g);
+
+// dx_s from sums[s] (after the group's one all_reduce) and count[s].
+std::vector<at::Tensor> batch_norm_backward_elemt_act_grouped(
+    const std::vector<at::Tensor>& grad_outs,
+    const std::vector<at::Tensor>& inputs, const at::Tensor& mean,
+    const at::Tensor& invstd, const at::Tensor& coefs, const at::Tensor& sums,
+    const at::Tensor& count, bool relu);
+
+// launch_plan for the kinds "stats_grouped", "elemt_grouped",
+// "bwd_reduce_grouped" and "bwd_elemt_grouped".
+std::tuple<std::string, std::map<std::string, int64_t>> launch_plan_grouped(
+    const std::string& kind, const at::Tensor& input,
+    const std::vector<c10::optional<at::Tensor>>& others);
+
 // ---- launch plan (host only, launches nothing) ----------------------------
 // Which kernel path a call would take and how far its loops run, decided by
 // the same host code the ops launch with.  kind / tensors:
@@ -367,6 +434,10 @@ void batch_norm_stats_packed_from_partials(const at::Tensor& partials,
 //   "conv1x1_stats"      input = x,      others = {weight}: path "mfma" with
 //                        nchunks, row_tile, slab, nslabs, tiles_per_block,
 //                        k_trips and lds_bytes, or "ineligible"
+//   "stats_grouped" / "elemt_grouped"          input = x_0, others = {x_1 ..
+//                        x_{S-1}}; "bwd_reduce_grouped" / "bwd_elemt_grouped"
+//                        others = {x_1 .. x_{S-1}, dy_0 .. dy_{S-1}}: path
+//                        "nhwc" or "ineligible" (launch_plan_grouped)
 // (pass only what the op itself would dereference).  Returns (path, numbers):
 // path is "nchw_vec" | "nchw_flat" | "nhwc" | "small_plane" | "ineligible";
 // the dual kinds report "nhwc" with their single counterparts' numbers plus

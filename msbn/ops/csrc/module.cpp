@@ -129,6 +129,30 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         &msbn::batch_norm_stats_packed_from_partials, py::arg("partials"),
         py::arg("nchunks"), py::arg("count"), py::arg("eps"), py::arg("out"));
 
+  m.def("batch_norm_stats_local_grouped",
+        &msbn::batch_norm_stats_local_grouped, py::arg("inputs"),
+        py::arg("eps"), py::arg("running_mean"), py::arg("running_var"),
+        py::arg("momentum"), py::arg("weight"), py::arg("bias"));
+  m.def("batch_norm_stats_packed_grouped",
+        &msbn::batch_norm_stats_packed_grouped, py::arg("inputs"),
+        py::arg("eps"), py::arg("out"));
+  m.def("batch_norm_gather_stats_packed_grouped",
+        &msbn::batch_norm_gather_stats_packed_grouped, py::arg("packed_all"),
+        py::arg("running_mean"), py::arg("running_var"), py::arg("momentum"),
+        py::arg("eps"), py::arg("weight"), py::arg("bias"));
+  m.def("batch_norm_elemt_act_grouped", &msbn::batch_norm_elemt_act_grouped,
+        py::arg("inputs"), py::arg("coefs"), py::arg("relu"));
+  m.def("batch_norm_backward_reduce_act_grouped",
+        &msbn::batch_norm_backward_reduce_act_grouped, py::arg("grad_outs"),
+        py::arg("inputs"), py::arg("mean"), py::arg("invstd"),
+        py::arg("coefs"), py::arg("relu"), py::arg("weight_g"),
+        py::arg("bias_g"));
+  m.def("batch_norm_backward_elemt_act_grouped",
+        &msbn::batch_norm_backward_elemt_act_grouped, py::arg("grad_outs"),
+        py::arg("inputs"), py::arg("mean"), py::arg("invstd"),
+        py::arg("coefs"), py::arg("sums"), py::arg("count"),
+        py::arg("relu"));
+
   m.def("bn_frozen_coefs", &msbn::bn_frozen_coefs, py::arg("running_mean"),
         py::arg("running_var"), py::arg("eps"), py::arg("weight"),
         py::arg("bias"));
