@@ -186,13 +186,29 @@ def _check_negative_slope(relu: bool, negative_slope) -> float:
     return negative_slope
 
 
+def _check_act(relu: bool, negative_slope: float, act) -> Optional[str]:
+    """Validate a module's ``act`` keyword (None, or "silu" for a fused SiLU
+    epilogue in the place of the ReLU / LeakyReLU); returns it."""
+    if act is None:
+        return None
+    if act != "silu":
+        raise ValueError(f"act must be None or 'silu' (got {act!r})")
+    if not relu:
+        raise ValueError("act='silu' is the fused activation: it needs "
+                         "relu=True")
+    if negative_slope != 0.0:
+        raise ValueError("act='silu' has no slope: negative_slope must be 0")
+    return act
+
+
 def _composed_running_stats_forward(
     input: Tensor, residual: Optional[Tensor], weight, bias, running_mean,
     running_var, eps: float, relu: bool, negative_slope: float = 0.0,
+    act: Optional[str] = None,
 ) -> Tensor:
     """Differentiable eager expression of act?(bn_running(x) [+ residual]),
-    act = ReLU or LeakyReLU(negative_slope): the CPU path, and the GPU A/B
-    baseline under MSBN_FROZEN_COMPOSED=1."""
+    act = ReLU, LeakyReLU(negative_slope) or SiLU: the CPU path, and the GPU
+    A/B baseline under MSBN_FROZEN_COMPOSED=1."""
     rm = running_mean.to(torch.float32)
     rv = running_var.to(torch.float32)
     invstd = torch.rsqrt(rv + eps)
@@ -209,7 +225,9 @@ def _composed_running_stats_forward(
     out = input.to(torch.float32) * scale.reshape(shape) + shift.reshape(shape)
     if residual is not None:
         out = out + residual.to(torch.float32)
-    if relu:
+    if relu and act == "silu":
+        out = torch.nn.functional.silu(out)
+    elif relu:
         if negative_slope == 0.0:
             out = torch.relu(out)
         else:
@@ -219,10 +237,10 @@ def _composed_running_stats_forward(
 
 def _running_stats_forward(
     module, input: Tensor, residual: Optional[Tensor], relu: bool,
-    negative_slope: float = 0.0,
+    negative_slope: float = 0.0, act: Optional[str] = None,
 ) -> Tensor:
     """Normalize with the module's running statistics (eval mode / frozen),
-    then the optional fused ReLU / LeakyReLU(negative_slope):
+    then the optional fused ReLU / LeakyReLU(negative_slope) / SiLU (``act``):
 
       * GPU, autograd on  -> FrozenBatchNormActFunction (coefs kernel + one
         elemt launch forward, one elementwise kernel backward);
@@ -240,18 +258,18 @@ def _running_stats_forward(
         invstd = torch.rsqrt(module.running_var.to(torch.float32) + module.eps)
         return _ops.batch_norm_elemt_act(
             input, residual, module.weight, module.bias, rm, invstd, relu,
-            None, negative_slope,
+            None, negative_slope, act=act,
         )
     if input.is_cuda and not _FROZEN_COMPOSED:
         from msbn.nn.frozen import FrozenBatchNormActFunction
 
         return FrozenBatchNormActFunction.apply(
             input, residual, module.weight, module.bias, module.running_mean,
-            module.running_var, module.eps, relu, negative_slope,
+            module.running_var, module.eps, relu, negative_slope, act,
         )
     return _composed_running_stats_forward(
         input, residual, module.weight, module.bias, module.running_mean,
-        module.running_var, module.eps, relu, negative_slope,
+        module.running_var, module.eps, relu, negative_slope, act,
     )
 
 

@@ -11,7 +11,9 @@ The detection fine-tuning recipe (frozen backbone BN) and any BatchNorm in
             kernel never reads x, so the input is not kept alive.
 
 A non-zero ``negative_slope`` turns the ReLU into LeakyReLU (forward
-z>0 ? z : slope*z, gate z>0 ? dy : slope*dy) in the same kernels.
+z>0 ? z : slope*z, gate z>0 ? dy : slope*dy) in the same kernels, and
+``act="silu"`` into SiLU (forward z*sigmoid(z), backward dy*silu'(z)
+recomputed from x like the gate).
 
 With fixed statistics there are no batch reductions.  Only when the affine
 parameters themselves need a gradient (a trainable BN put in ``.eval()``)
@@ -29,8 +31,8 @@ import torch
 from torch.nn import Module
 
 from msbn import ops
-from msbn.nn.batchnorm import (_NormBase, _check_negative_slope,
-                               _running_stats_forward)
+from msbn.nn.batchnorm import (_NormBase, _check_act,
+                               _check_negative_slope, _running_stats_forward)
 from msbn.nn.functions import _contig, _match_layout
 
 
@@ -43,20 +45,21 @@ def _dense_format(t: torch.Tensor) -> torch.memory_format:
     return torch.contiguous_format
 
 
-def _elemt(input, residual, coefs, relu: bool, negative_slope: float = 0.0):
+def _elemt(input, residual, coefs, relu: bool, negative_slope: float = 0.0,
+           act: Optional[str] = None):
     C = int(input.shape[1])
     scale, shift = coefs[:C], coefs[C:]
     if input.is_cuda:
         # mean / invstd / weight / bias are not consulted when coefs is given
         return ops.batch_norm_elemt_act(
             input, residual, None, None, scale, scale, relu, coefs,
-            negative_slope,
+            negative_slope, act=act,
         )
     # CPU reference takes (mean, invstd, weight, bias): mean=0, invstd=scale,
     # bias=shift reproduces x*scale + shift
     return ops.batch_norm_elemt_act(
         input, residual, None, shift, torch.zeros_like(scale), scale, relu,
-        None, negative_slope,
+        None, negative_slope, act=act,
     )
 
 
@@ -78,8 +81,10 @@ class FrozenBatchNormActFunction(torch.autograd.Function):
         eps: float,
         relu: bool,
         negative_slope: float = 0.0,
+        act: Optional[str] = None,
     ):
         ctx.negative_slope = negative_slope
+        ctx.act = act
         input = _contig(input)
         if residual is not None:
             residual = _match_layout(residual, input)
@@ -114,7 +119,7 @@ class FrozenBatchNormActFunction(torch.autograd.Function):
         ctx.memory_format = _dense_format(input)
         if input.numel() == 0:
             return torch.empty_like(input)
-        return _elemt(input, residual, coefs, relu, negative_slope)
+        return _elemt(input, residual, coefs, relu, negative_slope, act)
 
     @staticmethod
     def backward(ctx, grad_output: torch.Tensor):
@@ -135,7 +140,7 @@ class FrozenBatchNormActFunction(torch.autograd.Function):
                 torch.empty_like(grad_output) if need_res_g else None,
                 torch.zeros_like(weight) if need_weight_g else None,
                 torch.zeros_like(bias) if need_bias_g else None,
-                None, None, None, None, None,
+                None, None, None, None, None, None,
             )
 
         grad_weight = grad_bias = None
@@ -143,7 +148,8 @@ class FrozenBatchNormActFunction(torch.autograd.Function):
             # trainable affine under fixed statistics: the existing reduce
             # kernel with mean=running_mean, invstd=rsqrt(running_var+eps)
             # gives grad_weight / grad_bias and writes the masked gradient
-            # gm = dy*1[z>0]; the elementwise pass then runs gate-free on gm.
+            # gm = dy*1[z>0] (SiLU: dy*silu'(z), rounded to the activation
+            # dtype); the elementwise pass then runs gate-free on gm.
             want_elemt = need_input_g or need_res_g
             mean = running_mean.to(torch.float32)
             invstd = torch.rsqrt(running_var.to(torch.float32) + ctx.eps)
@@ -152,6 +158,7 @@ class FrozenBatchNormActFunction(torch.autograd.Function):
             _, _, grad_weight, grad_bias = ops.batch_norm_backward_reduce_act(
                 grad_output, input, residual, mean, invstd, weight, bias,
                 relu, False, need_weight_g, need_bias_g, coefs, gm, slope,
+                act=ctx.act if relu else None,
             )
             if gm is not None:
                 grad_output, relu = gm, False
@@ -161,14 +168,14 @@ class FrozenBatchNormActFunction(torch.autograd.Function):
             grad_input, grad_res = ops.batch_norm_frozen_backward_elemt(
                 grad_output, input if relu else None,
                 residual if relu else None, coefs, relu, need_input_g,
-                need_res_g, slope,
+                need_res_g, slope, ctx.act if relu else None,
             )
         return (
             grad_input,
             grad_res,
             grad_weight if need_weight_g else None,
             grad_bias if need_bias_g else None,
-            None, None, None, None, None,
+            None, None, None, None, None, None,
         )
 
 
@@ -176,7 +183,8 @@ class FrozenBatchNorm2d(_NormBase):
     """BatchNorm with fixed statistics AND fixed affine (+ optional fused
     residual-add / ReLU epilogue): ``forward(x, residual=None)`` ==
     ``relu?(bn_eval(x) [+ residual])`` whatever ``.training`` says.
-    ``relu=True, negative_slope=s`` makes the activation LeakyReLU(s).
+    ``relu=True, negative_slope=s`` makes the activation LeakyReLU(s);
+    ``act="silu"`` makes it SiLU (and turns it on).
 
     ``weight``, ``bias``, ``running_mean``, ``running_var`` and
     ``num_batches_tracked`` are buffers (zero parameters) under the same
@@ -189,7 +197,8 @@ class FrozenBatchNorm2d(_NormBase):
 
     def __init__(self, num_features: int, eps: float = 1e-5,
                  relu: bool = False, device=None, dtype=None,
-                 negative_slope: float = 0.0) -> None:
+                 negative_slope: float = 0.0,
+                 act: Optional[str] = None) -> None:
         # buffers instead of _NormBase's parameters: no _NormBase.__init__
         Module.__init__(self)
         factory_kwargs = {"device": device, "dtype": dtype}
@@ -198,8 +207,10 @@ class FrozenBatchNorm2d(_NormBase):
         self.momentum = 0.0
         self.affine = True
         self.track_running_stats = True
+        relu = bool(relu) or act is not None
         self.relu = relu
         self.negative_slope = _check_negative_slope(relu, negative_slope)
+        self.act = _check_act(relu, self.negative_slope, act)
         self.register_buffer("weight",
                              torch.ones(num_features, **factory_kwargs))
         self.register_buffer("bias",
@@ -229,6 +240,8 @@ class FrozenBatchNorm2d(_NormBase):
         slope = getattr(self, "negative_slope", 0.0)
         if slope != 0.0:
             s += f", negative_slope={slope}"
+        if getattr(self, "act", None) is not None:
+            s += f", act={self.act!r}"
         return s
 
     def _load_from_state_dict(
@@ -248,15 +261,15 @@ class FrozenBatchNorm2d(_NormBase):
     def forward(self, input: torch.Tensor,
                 residual: Optional[torch.Tensor] = None) -> torch.Tensor:
         self._check_input_dim(input)
-        # default: modules pickled before negative_slope existed
+        # defaults: modules pickled before negative_slope / act existed
         return _running_stats_forward(
             self, input, residual, self.relu,
-            getattr(self, "negative_slope", 0.0),
+            getattr(self, "negative_slope", 0.0), getattr(self, "act", None),
         )
 
 
-def _frozen_from(bn, relu: bool,
-                 negative_slope: float = 0.0) -> FrozenBatchNorm2d:
+def _frozen_from(bn, relu: bool, negative_slope: float = 0.0,
+                 act: Optional[str] = None) -> FrozenBatchNorm2d:
     """A FrozenBatchNorm2d sharing ``bn``'s tensors."""
     if not bn.track_running_stats or bn.running_mean is None:
         raise ValueError(
@@ -266,7 +279,7 @@ def _frozen_from(bn, relu: bool,
     out = FrozenBatchNorm2d(bn.num_features, bn.eps, relu=relu,
                             device=bn.running_mean.device,
                             dtype=bn.running_mean.dtype,
-                            negative_slope=negative_slope)
+                            negative_slope=negative_slope, act=act)
     if bn.weight is not None:
         out.weight = bn.weight.detach()
     if bn.bias is not None:
@@ -285,7 +298,7 @@ def freeze_batchnorm(module: Module) -> Module:
     """Recursively replace every BatchNorm (torch.nn BatchNorm1d/2d/3d and
     SyncBatchNorm; msbn BatchNorm*, SyncBatchNorm and SyncBatchNormAct2d)
     with a ``FrozenBatchNorm2d`` that shares its tensors and keeps a fused
-    ReLU / LeakyReLU epilogue.  ``affine=False`` becomes ones / zeros buffers; a source
+    ReLU / LeakyReLU / SiLU epilogue.  ``affine=False`` becomes ones / zeros buffers; a source
     without running statistics raises."""
     out = module
     targets = (torch.nn.modules.batchnorm._BatchNorm, _NormBase)
@@ -295,6 +308,7 @@ def freeze_batchnorm(module: Module) -> Module:
         out = _frozen_from(
             module, relu,
             getattr(module, "negative_slope", 0.0) if relu else 0.0,
+            getattr(module, "act", None) if relu else None,
         )
     for name, child in module.named_children():
         out.add_module(name, freeze_batchnorm(child))

@@ -1,8 +1,9 @@
 """fuse_bn_act: graph-free module-tree pass that merges adjacent
-(BatchNorm2d | SyncBatchNorm, ReLU | LeakyReLU) pairs inside nn.Sequential
-containers into a single SyncBatchNormAct2d (one-kernel epilogue, identical
-math).  A LeakyReLU's ``negative_slope`` is carried into the fused module;
-``inplace`` is irrelevant for either activation.  A (FrozenBatchNorm2d,
+(BatchNorm2d | SyncBatchNorm, ReLU | LeakyReLU | SiLU) pairs inside
+nn.Sequential containers into a single SyncBatchNormAct2d (one-kernel
+epilogue, identical math).  A LeakyReLU's ``negative_slope`` is carried into
+the fused module and a SiLU becomes ``act="silu"``; the activation module's
+``inplace`` is irrelevant.  A (FrozenBatchNorm2d,
 ReLU | LeakyReLU) pair becomes a FrozenBatchNorm2d(relu=True[,
 negative_slope=s]).  ``fuse_bn_act(model, inplace=True)`` makes the
 (BN, LeakyReLU) pairs in-place modules (the output overwrites the input, the
@@ -23,24 +24,25 @@ from msbn.nn.frozen import FrozenBatchNorm2d, _frozen_from
 from msbn.nn.fused import SyncBatchNormAct2d
 
 
-_ACTS = (nn.ReLU, nn.LeakyReLU)
+_ACTS = (nn.ReLU, nn.LeakyReLU, nn.SiLU)
 
 
 def _to_act(bn, act_module, inplace=False):
     relu = isinstance(act_module, _ACTS)
     slope = (float(act_module.negative_slope)
              if isinstance(act_module, nn.LeakyReLU) else 0.0)
+    act = "silu" if isinstance(act_module, nn.SiLU) else None
     if isinstance(bn, FrozenBatchNorm2d):
         # frozen stays frozen: same tensors, activation folded into the
         # epilogue
-        return _frozen_from(bn, relu=relu, negative_slope=slope)
+        return _frozen_from(bn, relu=relu, negative_slope=slope, act=act)
     out = SyncBatchNormAct2d(
         bn.num_features, bn.eps, bn.momentum, bn.affine,
         bn.track_running_stats,
         getattr(bn, "process_group", None),
-        relu=relu, negative_slope=slope,
+        relu=relu, negative_slope=slope, act=act,
         # only what the in-place backward can invert; the rest (plain ReLU,
-        # no affine) fuses out of place as ever
+        # SiLU, no affine) fuses out of place as ever
         inplace=inplace and bn.affine and slope > 0.0,
     )
     if bn.affine:
@@ -62,14 +64,15 @@ def _fusable_bn(m) -> bool:
 
 
 def fuse_bn_act(module: nn.Module, inplace: bool = False) -> nn.Module:
-    """Recursively fuse (BN, ReLU) and (BN, LeakyReLU) pairs inside
-    Sequential containers.
+    """Recursively fuse (BN, ReLU), (BN, LeakyReLU) and (BN, SiLU) pairs
+    inside Sequential containers.
 
     ``inplace=True`` turns every (BN, LeakyReLU) pair with a positive slope
     and an affine BN into an in-place module
     (``SyncBatchNormAct2d(inplace=True)``: the output overwrites the input
     and the backward runs from the output, one activation tensor less per
-    layer); (BN, ReLU) pairs are fused out of place as without it.  Two
+    layer); (BN, ReLU) and (BN, SiLU) pairs are fused out of place as
+    without it.  Two
     preconditions the kernels cannot check: every channel's ``weight`` must
     be non-zero (a zero-initialised BN is incompatible: finite but wrong
     gradients for that channel), and the BN's input must not be needed by its

@@ -22,8 +22,9 @@ import torch
 import torch.distributed as dist
 
 from msbn import ops
-from msbn.nn.batchnorm import (SyncBatchNorm, _check_negative_slope,
-                               _momentum_factor, _running_stats_forward)
+from msbn.nn.batchnorm import (SyncBatchNorm, _check_act,
+                               _check_negative_slope, _momentum_factor,
+                               _running_stats_forward)
 from msbn.nn.functions import (_combined_view, _contig, _force_sync,
                                _match_layout, compute_sync_stats)
 
@@ -48,8 +49,13 @@ class SyncBatchNormActFunction(torch.autograd.Function):
         gate_bits: bool = False,
         partials: Optional[torch.Tensor] = None,
         nchunks: Optional[int] = None,
+        act: Optional[str] = None,
     ):
-        """``partials`` / ``nchunks``: ``input`` came out of
+        """``act="silu"`` (with ``relu`` and a zero slope) makes the epilogue
+        SiLU: always the two-stage kernels, no gate bits (it has no branch),
+        and the backward recomputes silu'(z) where ReLU recomputes its gate.
+
+        ``partials`` / ``nchunks``: ``input`` came out of
         ``ops.conv1x1_stats`` together with these per-channel partial sums;
         the statistics are finalized from them instead of read from
         ``input`` (``compute_sync_stats``), always on the two-stage route.
@@ -75,7 +81,7 @@ class SyncBatchNormActFunction(torch.autograd.Function):
         y = SyncBatchNormActFunction._forward(
             ctx, input, residual, weight, bias, running_mean, running_var,
             eps, momentum, process_group, world_size, relu, negative_slope,
-            partials, nchunks,
+            partials, nchunks, act,
         )
         if not fork:
             return y
@@ -86,8 +92,9 @@ class SyncBatchNormActFunction(torch.autograd.Function):
     @staticmethod
     def _forward(ctx, input, residual, weight, bias, running_mean,
                  running_var, eps, momentum, process_group, world_size, relu,
-                 negative_slope, partials=None, nchunks=None):
+                 negative_slope, partials=None, nchunks=None, act=None):
         ctx.negative_slope = negative_slope
+        ctx.act = act = _check_act(relu, negative_slope, act)
         ctx.has_res = residual is not None
         ctx.has_gate = False
         input = _contig(input)
@@ -104,6 +111,7 @@ class SyncBatchNormActFunction(torch.autograd.Function):
         if (
             not use_sync
             and partials is None  # the statistics exist already
+            and act is None  # the single-launch kernels have no SiLU
             and input.numel() > 0
             and (residual is None or residual.is_contiguous())
             and ops.bn_fused_local_eligible(
@@ -145,7 +153,8 @@ class SyncBatchNormActFunction(torch.autograd.Function):
         gate = None
         if input.numel() == 0:
             y = torch.empty_like(input)
-        elif (ctx.gate_bits and relu and residual is not None
+        elif (ctx.gate_bits and relu and act is None
+                and residual is not None
                 and ctx.needs_input_grad[1] and input.is_cuda):
             y, gate = ops.batch_norm_elemt_act(
                 input, residual, weight, bias, mean, invstd, relu, coefs,
@@ -154,7 +163,7 @@ class SyncBatchNormActFunction(torch.autograd.Function):
         else:
             y = ops.batch_norm_elemt_act(
                 input, residual, weight, bias, mean, invstd, relu, coefs,
-                negative_slope,
+                negative_slope, act=act,
             )
         ctx.has_gate = gate is not None
         saved = (input, None if ctx.has_gate else residual, weight, bias,
@@ -171,7 +180,7 @@ class SyncBatchNormActFunction(torch.autograd.Function):
         if grad_output is None:  # fork with only the second output used
             grad_output, grad_skip = grad_skip, None
         if grad_output is None:
-            return (None,) * 16
+            return (None,) * 17
         saved = ctx.saved_tensors
         input, residual, weight, bias, mean, invstd, count_sum = saved[:7]
         coefs = saved[7] if ctx.has_coefs else None
@@ -188,12 +197,13 @@ class SyncBatchNormActFunction(torch.autograd.Function):
         )
         # The fold needs gm (below).  gm holds the gated gradient rounded to
         # the activation dtype: exact for none / relu (the gate passes or
-        # zeroes a value that already is one), but slope*g is not, so a leaky
-        # layer that would not have materialized gm anyway keeps the eager
-        # add and its fp32 gate.
-        if fold and ctx.relu and ctx.negative_slope != 0.0 and not (
-            has_res and ctx.needs_input_grad[1]
-        ):
+        # zeroes a value that already is one), but slope*g and dy*silu'(z)
+        # are not, so a leaky or SiLU layer that would not have materialized
+        # gm anyway keeps the eager add and its fp32 derivative.
+        act = getattr(ctx, "act", None)
+        if fold and ctx.relu and (
+            ctx.negative_slope != 0.0 or act is not None
+        ) and not (has_res and ctx.needs_input_grad[1]):
             fold = False
         if grad_skip is not None and not fold:
             grad_output = grad_output + grad_skip
@@ -228,12 +238,12 @@ class SyncBatchNormActFunction(torch.autograd.Function):
                 grad_weight if need_weight_g else None,
                 grad_bias if need_bias_g else None,
                 None, None, None, None, None, None, None, None, None, None,
-                None, None,
+                None, None, None,
             )
 
         # Masked-grad materialization: when the residual branch needs its
         # gradient, the reduce pass writes gm = dy*1[z>0] (leaky: slope*dy
-        # where z<=0) once; the elemt pass then reads gm instead of
+        # where z<=0; SiLU: dy*silu'(z), rounded to the dtype) once; the elemt pass then reads gm instead of
         # (dy, residual) and gm itself IS the residual gradient -> one fewer
         # full-tensor read+write (8A -> 7A).
         # With both fork gradients (fold) gm is always written: the reduce
@@ -262,7 +272,7 @@ class SyncBatchNormActFunction(torch.autograd.Function):
                 torch.zeros_like(weight) if need_weight_g else None,
                 torch.zeros_like(bias) if need_bias_g else None,
                 None, None, None, None, None, None, None, None, None, None,
-                None, None,
+                None, None, None,
             )
         gm = torch.empty_like(grad_output) if use_gm else None
         if gate is not None:
@@ -279,7 +289,7 @@ class SyncBatchNormActFunction(torch.autograd.Function):
                 ops.batch_norm_backward_reduce_act(
                     grad_output, input, residual, mean, invstd, weight, bias,
                     relu, need_input_g, need_weight_g, need_bias_g, coefs, gm,
-                    slope, grad_skip,
+                    slope, grad_skip, None, act,
                 )
             )
         grad_input = grad_res = None
@@ -306,7 +316,7 @@ class SyncBatchNormActFunction(torch.autograd.Function):
                 grad_input, grad_res = ops.batch_norm_backward_elemt_act(
                     grad_output, input, residual, mean, invstd, weight, bias,
                     sum_dy, sum_dy_xmu, count_sum, relu, need_res_g, coefs,
-                    slope,
+                    slope, act,
                 )
         return (
             grad_input if need_input_g else None,
@@ -314,7 +324,7 @@ class SyncBatchNormActFunction(torch.autograd.Function):
             grad_weight if need_weight_g else None,
             grad_bias if need_bias_g else None,
             None, None, None, None, None, None, None, None, None, None,
-            None, None,
+            None, None, None,
         )
 
 
@@ -444,6 +454,7 @@ def stem_pool_eligible(bn, pool, input: torch.Tensor) -> bool:
     return (
         type(bn) is SyncBatchNormAct2d
         and not getattr(bn, "inplace", False)
+        and getattr(bn, "act", None) is None  # the pool kernels have no SiLU
         and not _hooked(bn) and not _hooked(pool)
         and (bn.training
              or (bn.running_mean is None and bn.running_var is None))
@@ -757,6 +768,7 @@ def dual_bn_eligible(bn, bn_skip, x: torch.Tensor) -> bool:
         type(bn) is SyncBatchNormAct2d and type(bn_skip) is SyncBatchNorm
         and bn.training and bn_skip.training
         and bn.relu and getattr(bn, "negative_slope", 0.0) == 0.0
+        and getattr(bn, "act", None) is None
         and getattr(bn, "gate_bits", False)
         and not getattr(bn, "inplace", False)
         and not _hooked(bn) and not _hooked(bn_skip)
@@ -856,6 +868,7 @@ def _bn_from_partials(bn, y, residual, fork, partials):
         _momentum_factor(bn), process_group, world_size,
         getattr(bn, "relu", False), getattr(bn, "negative_slope", 0.0), fork,
         getattr(bn, "gate_bits", False), partials, int(partials.shape[1]),
+        getattr(bn, "act", None),
     )
 
 
@@ -1068,7 +1081,8 @@ def _grouped_route(bn, xs, relu: bool) -> bool:
     """Whether ``bn_act_grouped`` takes the grouped kernels, from what is
     equal on every rank of a group by construction: the module's type and
     configuration (a training-mode out-of-place SyncBatchNorm,
-    SyncBatchNormAct2d without a slope, or a non-sync msbn BatchNorm; a float
+    SyncBatchNormAct2d without a slope or ``act``, or a non-sync msbn
+    BatchNorm; a float
     momentum; fp32 parameters and running statistics; no hooks), S, C, the
     dtype, the dimensionality and the device type.  Never a size."""
     from msbn.nn.batchnorm import _BatchNorm
@@ -1078,6 +1092,7 @@ def _grouped_route(bn, xs, relu: bool) -> bool:
          or (type(bn) is SyncBatchNormAct2d
              and not getattr(bn, "inplace", False)
              and getattr(bn, "negative_slope", 0.0) == 0.0
+             and getattr(bn, "act", None) is None
              and relu == bn.relu))
         and bn.training and not _hooked(bn)
         and isinstance(bn.momentum, float)
@@ -1113,7 +1128,7 @@ def bn_act_grouped(bn, xs, relu: Optional[bool] = None):
     Grouped: training mode, a float momentum, fp32 parameters, 1 <= S <= 8
     dense channels-last 4-D GPU tensors (fp32 / bf16 / half) with C a
     multiple of the 16-byte pack.  Everything else -- a residual or fork, an
-    in-place or LeakyReLU module, NCHW, ``momentum=None``, S > 8, CPU
+    in-place, LeakyReLU or SiLU module, NCHW, ``momentum=None``, S > 8, CPU
     tensors -- runs the loop.  With collectives in play the route is chosen
     from rank-equal properties only (``_grouped_route``); a tensor that is
     then not dense channels-last on a 16-byte boundary is copied, never
@@ -1277,8 +1292,14 @@ class SyncBatchNormAct2d(SyncBatchNorm):
 
     forward(x, residual=None) == relu(bn(x) + residual) with identical math.
     ``relu=True, negative_slope=s`` makes the activation LeakyReLU(s):
-    leaky_relu(bn(x) + residual, s).  The slope is a hyper-parameter, not
-    state: state-dict keys are those of SyncBatchNorm.
+    leaky_relu(bn(x) + residual, s), and ``act="silu"`` (zero slope) makes
+    it SiLU: silu(bn(x) + residual).  Both are hyper-parameters, not state:
+    state-dict keys are those of SyncBatchNorm.
+
+    A SiLU layer always takes the two-stage kernels (a known cost for planes
+    <= 16K elements, as for in-place layers), keeps no gate bits, and the
+    stem-pool, dual and grouped routes run their composition for it.  It
+    cannot be ``inplace`` (SiLU is not invertible).
 
     ``inplace=True`` (In-Place Activated BatchNorm) writes the output over
     the input in training mode and runs the backward from the output, so the
@@ -1305,7 +1326,8 @@ class SyncBatchNormAct2d(SyncBatchNorm):
     def __init__(self, num_features, eps=1e-5, momentum=0.1, affine=True,
                  track_running_stats=True, process_group=None, device=None,
                  dtype=None, relu: bool = True, negative_slope: float = 0.0,
-                 inplace: bool = False, gate_bits: bool = True):
+                 inplace: bool = False, gate_bits: bool = True,
+                 act: Optional[str] = None):
         super().__init__(num_features, eps, momentum, affine,
                          track_running_stats, process_group, device, dtype)
         # keep the activation's branch as one bit per element instead of the
@@ -1314,9 +1336,15 @@ class SyncBatchNormAct2d(SyncBatchNorm):
         self.gate_bits = bool(gate_bits)
         self.relu = relu
         self.negative_slope = _check_negative_slope(relu, negative_slope)
+        self.act = _check_act(relu, self.negative_slope, act)
         if inplace:
             if not affine:
                 raise ValueError("inplace=True requires affine=True")
+            if self.act is not None:
+                raise ValueError(
+                    "inplace=True needs an invertible activation: "
+                    f"act={self.act!r} cannot be inverted"
+                )
             if relu and not self.negative_slope > 0.0:
                 raise ValueError(
                     "inplace=True needs an invertible activation: "
@@ -1330,6 +1358,8 @@ class SyncBatchNormAct2d(SyncBatchNorm):
         slope = getattr(self, "negative_slope", 0.0)
         if slope != 0.0:
             s += f", negative_slope={slope}"
+        if getattr(self, "act", None) is not None:
+            s += f", act={self.act!r}"
         if getattr(self, "inplace", False):
             s += ", inplace=True"
         return s
@@ -1344,8 +1374,9 @@ class SyncBatchNormAct2d(SyncBatchNorm):
         self._check_non_zero_input_channels(input)
         # default: modules pickled before negative_slope existed
         slope = getattr(self, "negative_slope", 0.0)
-        # likewise for inplace
+        # likewise for inplace and act
         inplace = getattr(self, "inplace", False)
+        act = getattr(self, "act", None)
         if inplace and (residual is not None or fork):
             raise ValueError(
                 "an inplace=True SyncBatchNormAct2d takes neither a residual "
@@ -1366,7 +1397,7 @@ class SyncBatchNormAct2d(SyncBatchNorm):
             # the frozen kernels take one gradient: both consumers hang off
             # the same tensor and autograd sums for them, as ever
             y = _running_stats_forward(self, input, residual, self.relu,
-                                       slope)
+                                       slope, act)
             return (y, y) if fork else y
 
         process_group = None
@@ -1387,5 +1418,5 @@ class SyncBatchNormAct2d(SyncBatchNorm):
             self.eps, factor, process_group, world_size, self.relu, slope,
             fork,
             # default: modules pickled before gate_bits existed
-            getattr(self, "gate_bits", False),
+            getattr(self, "gate_bits", False), None, None, act,
         )

@@ -212,6 +212,14 @@ def bn_make_coefs(mean, invstd, weight, bias):
     return None
 
 
+def _act_name(relu: bool, negative_slope: float, act: Optional[str]) -> str:
+    """The extension's spelling of ``act`` ("" for None), validated here so
+    that CPU and GPU tensors raise alike."""
+    if act is None:  # the common case, on every BN layer's hot path
+        return ""
+    return "silu" if _ref.check_act(relu, negative_slope, act) else ""
+
+
 def gate_bits_empty(input: torch.Tensor) -> torch.Tensor:
     """An unwritten gate-bit tensor for ``input``: ``ceil(numel/8)`` uint8."""
     return torch.empty((input.numel() + 7) // 8, dtype=torch.uint8,
@@ -220,9 +228,13 @@ def gate_bits_empty(input: torch.Tensor) -> torch.Tensor:
 
 def batch_norm_elemt_act(input, residual, weight, bias, mean, invstd,
                          relu: bool, coefs=None, negative_slope: float = 0.0,
-                         gate_out=None):
+                         gate_out=None, act: Optional[str] = None):
     """y = act(x*scale + shift [+ residual]); ``relu`` turns the activation
     on and ``negative_slope`` (only consulted then) makes it a LeakyReLU.
+    ``act`` names an activation the pair cannot: ``None`` is ``(relu,
+    negative_slope)`` as ever, ``"silu"`` (with ``relu`` true and a zero
+    slope) is y = z*sigmoid(z).  SiLU has no branch, so it never writes gate
+    bits.
 
     ``gate_out`` (``gate_bits_empty(input)``) asks the kernel to also store
     which branch the activation took, one bit per element: bit ``e & 7`` of
@@ -237,11 +249,12 @@ def batch_norm_elemt_act(input, residual, weight, bias, mean, invstd,
     if input.is_cuda:
         y, wrote = _require_hip().batch_norm_elemt_act(
             input, residual, weight, bias, mean, invstd, relu, coefs,
-            negative_slope, gate_out,
+            negative_slope, gate_out, _act_name(relu, negative_slope, act),
         )
         return y if gate_out is None else (y, gate_out if wrote else None)
     y = _ref.batch_norm_elemt_act(
-        input, residual, weight, bias, mean, invstd, relu, negative_slope
+        input, residual, weight, bias, mean, invstd, relu, negative_slope,
+        act,
     )
     return y if gate_out is None else (y, None)
 
@@ -250,8 +263,12 @@ def batch_norm_backward_reduce_act(grad_out, input, residual, mean, invstd,
                                    weight, bias, relu_mask, input_g, weight_g,
                                    bias_g, coefs=None, gm_out=None,
                                    negative_slope: float = 0.0,
-                                   grad_out2=None, gate=None, *, dual=None):
-    """First pass of the fused BN backward.  ``grad_out2`` is the second
+                                   grad_out2=None, gate=None,
+                                   act: Optional[str] = None, *, dual=None):
+    """First pass of the fused BN backward.  ``act`` as in
+    ``batch_norm_elemt_act``; ``"silu"`` takes neither ``gate`` nor ``dual``,
+    and its ``gm_out`` is g = dy*silu'(z) rounded to the input dtype (as
+    LeakyReLU's, not exact).  ``grad_out2`` is the second
     gradient of a forked output, delivered unsummed: the incoming gradient is
     ``grad_out + grad_out2`` rounded to the input dtype once (the tensor an
     eager add would have produced), read inside the reduce kernel instead of
@@ -275,6 +292,9 @@ def batch_norm_backward_reduce_act(grad_out, input, residual, mean, invstd,
     [C] vectors).  Inputs the dual kernel declines (a
     gradient off 16-byte alignment, ...) run the two single reduces; same
     results."""
+    act_name = _act_name(relu_mask, negative_slope, act)
+    if act_name and gate is not None:
+        raise ValueError("act='silu' has no single-bit gate")
     if dual is not None:
         if not input.is_cuda:
             raise ValueError("the dual reduce exists on the GPU path only")
@@ -299,30 +319,33 @@ def batch_norm_backward_reduce_act(grad_out, input, residual, mean, invstd,
         return _require_hip().batch_norm_backward_reduce_act(
             grad_out, input, residual, mean, invstd, weight, bias, relu_mask,
             input_g, weight_g, bias_g, coefs, gm_out, negative_slope,
-            grad_out2, gate,
+            grad_out2, gate, act_name,
         )
     if gate is not None:
         raise ValueError("gate bits exist on the GPU path only")
     return _ref.batch_norm_backward_reduce_act(
         grad_out, input, residual, mean, invstd, weight, bias, relu_mask,
-        input_g, weight_g, bias_g, gm_out, negative_slope, grad_out2,
+        input_g, weight_g, bias_g, gm_out, negative_slope, grad_out2, act,
     )
 
 
 def batch_norm_backward_elemt_act(grad_out, input, residual, mean, invstd,
                                   weight, bias, sum_dy, sum_dy_xmu, count,
                                   relu_mask, want_res_grad, coefs=None,
-                                  negative_slope: float = 0.0):
+                                  negative_slope: float = 0.0,
+                                  act: Optional[str] = None):
+    """Second pass: dx = a*g + b*x + d, dres = g, with g = grad_out through
+    the activation's derivative (``act`` as in ``batch_norm_elemt_act``)."""
     if input.is_cuda:
         dx, dres = _require_hip().batch_norm_backward_elemt_act(
             grad_out, input, residual, mean, invstd, weight, bias, sum_dy,
             sum_dy_xmu, count, relu_mask, want_res_grad, coefs,
-            negative_slope,
+            negative_slope, _act_name(relu_mask, negative_slope, act),
         )
         return dx, (dres if want_res_grad else None)
     return _ref.batch_norm_backward_elemt_act(
         grad_out, input, residual, mean, invstd, weight, bias, sum_dy,
-        sum_dy_xmu, count, relu_mask, want_res_grad, negative_slope,
+        sum_dy_xmu, count, relu_mask, want_res_grad, negative_slope, act,
     )
 
 
@@ -486,22 +509,25 @@ def bn_frozen_coefs(running_mean, running_var, eps: float, weight, bias):
 def batch_norm_frozen_backward_elemt(grad_out, input, residual, coefs,
                                      relu_mask: bool, want_input_grad: bool,
                                      want_res_grad: bool,
-                                     negative_slope: float = 0.0):
+                                     negative_slope: float = 0.0,
+                                     act: Optional[str] = None):
     """Backward of the frozen BN(+add)(+ReLU) epilogue, one elementwise pass:
     dx = scale*g, dres = g, g = grad_out*1[z>0] (LeakyReLU for a non-zero
-    ``negative_slope``: g = negative_slope*grad_out where z <= 0).  ``input``
+    ``negative_slope``: g = negative_slope*grad_out where z <= 0;
+    ``act="silu"``: g = grad_out*silu'(z)).  ``input``
     / ``residual`` are only needed for the gate (``relu_mask``); without it
     ``dres`` is ``grad_out`` itself.  Returns (dx-or-None, dres-or-None)."""
     if grad_out.is_cuda:
         dx, dres = _require_hip().batch_norm_frozen_backward_elemt(
             grad_out, input, residual, coefs, relu_mask, want_input_grad,
             want_res_grad, negative_slope,
+            _act_name(relu_mask, negative_slope, act),
         )
         return (dx if want_input_grad else None,
                 dres if want_res_grad else None)
     return _ref.batch_norm_frozen_backward_elemt(
         grad_out, input, residual, coefs, relu_mask, want_input_grad,
-        want_res_grad, negative_slope,
+        want_res_grad, negative_slope, act,
     )
 
 

@@ -139,19 +139,38 @@ def _act_coefs(mean, invstd, weight, bias):
     return scale, shift
 
 
+def check_act(relu: bool, negative_slope: float, act) -> bool:
+    """Validate an op's ``act`` keyword; True for the SiLU mode.  ``None`` is
+    the ``(relu, negative_slope)`` pair on its own."""
+    if act is None:
+        return False
+    if act != "silu":
+        raise ValueError(f"act must be None or 'silu' (got {act!r})")
+    if not relu or negative_slope != 0.0:
+        raise ValueError(
+            "act='silu' needs the activation flag set and a zero "
+            "negative_slope"
+        )
+    return True
+
+
 def batch_norm_elemt_act(
     input, residual, weight, bias, mean, invstd, relu: bool,
-    negative_slope: float = 0.0,
+    negative_slope: float = 0.0, act=None,
 ):
     """y = act?(x*scale + shift [+ residual]) — fused epilogue reference.
-    ``negative_slope`` (consulted only with ``relu``) selects LeakyReLU."""
+    ``negative_slope`` (consulted only with ``relu``) selects LeakyReLU,
+    ``act="silu"`` y = z*sigmoid(z)."""
+    silu = check_act(relu, negative_slope, act)
     scale, shift = _act_coefs(mean, invstd, weight, bias)
     z = input.to(torch.float32) * _chan_view(scale, input) + _chan_view(
         shift, input
     )
     if residual is not None:
         z = z + residual.to(torch.float32)
-    if relu:
+    if silu:
+        z = z * torch.sigmoid(z)
+    elif relu:
         if negative_slope == 0.0:
             z = torch.relu(z)
         else:
@@ -159,15 +178,20 @@ def batch_norm_elemt_act(
     return z.to(input.dtype)
 
 
-def _gate(z, g, negative_slope: float):
-    """g through the activation's gate; z == 0 takes the negative branch."""
+def _gate(z, g, negative_slope: float, silu: bool = False):
+    """g through the activation's gate; z == 0 takes the negative branch.
+    SiLU has no branch: g * sigmoid(z) * (1 + z*(1 - sigmoid(z)))."""
+    if silu:
+        sg = torch.sigmoid(z)
+        return g * sg * (1.0 + z * (1.0 - sg))
     if negative_slope == 0.0:
         return torch.where(z > 0, g, torch.zeros_like(g))
     return torch.where(z > 0, g, negative_slope * g)
 
 
 def _masked_grad(grad_out, input, residual, mean, invstd, weight, bias,
-                 relu_mask: bool, negative_slope: float = 0.0):
+                 relu_mask: bool, negative_slope: float = 0.0, act=None):
+    silu = check_act(relu_mask, negative_slope, act)
     g = grad_out.to(torch.float32)
     if relu_mask:
         scale, shift = _act_coefs(mean, invstd, weight, bias)
@@ -176,21 +200,21 @@ def _masked_grad(grad_out, input, residual, mean, invstd, weight, bias,
         )
         if residual is not None:
             z = z + residual.to(torch.float32)
-        g = _gate(z, g, negative_slope)
+        g = _gate(z, g, negative_slope, silu)
     return g
 
 
 def batch_norm_backward_reduce_act(
     grad_out, input, residual, mean, invstd, weight, bias, relu_mask,
     input_g, weight_g, bias_g, gm_out=None, negative_slope: float = 0.0,
-    grad_out2=None,
+    grad_out2=None, act=None,
 ):
     if grad_out2 is not None:
         # the two gradients of a forked output: summed in the input dtype
         # first (one rounding), as autograd's own accumulation would
         grad_out = grad_out + grad_out2
     g = _masked_grad(grad_out, input, residual, mean, invstd, weight, bias,
-                     relu_mask, negative_slope)
+                     relu_mask, negative_slope, act)
     if gm_out is not None:
         gm_out.copy_(g.to(grad_out.dtype))
     return batch_norm_backward_reduce(
@@ -201,9 +225,10 @@ def batch_norm_backward_reduce_act(
 def batch_norm_backward_elemt_act(
     grad_out, input, residual, mean, invstd, weight, bias, sum_dy,
     sum_dy_xmu, count, relu_mask, want_res_grad, negative_slope: float = 0.0,
+    act=None,
 ):
     g = _masked_grad(grad_out, input, residual, mean, invstd, weight, bias,
-                     relu_mask, negative_slope)
+                     relu_mask, negative_slope, act)
     dx = batch_norm_backward_elemt(
         g, input, mean, invstd, weight, sum_dy, sum_dy_xmu, count
     )
@@ -434,11 +459,14 @@ def bn_frozen_coefs(running_mean, running_var, eps: float, weight, bias):
 def batch_norm_frozen_backward_elemt(
     grad_out, input, residual, coefs, relu_mask: bool,
     want_input_grad: bool, want_res_grad: bool, negative_slope: float = 0.0,
+    act=None,
 ):
     """Backward of y = act?(x*scale + shift [+ residual]) with FIXED scale /
     shift: dx = scale*g, dres = g, g = grad_out * 1[z > 0] (or
-    negative_slope*grad_out where z <= 0).  ``input`` and ``residual`` are
-    only consulted for the gate (relu_mask)."""
+    negative_slope*grad_out where z <= 0; ``act="silu"``: grad_out *
+    silu'(z)).  ``input`` and ``residual`` are only consulted for the gate
+    (relu_mask)."""
+    silu = check_act(relu_mask, negative_slope, act)
     C = grad_out.shape[1]
     scale = _chan_view(coefs[:C], grad_out)
     g = grad_out.to(torch.float32)
@@ -446,7 +474,7 @@ def batch_norm_frozen_backward_elemt(
         z = input.to(torch.float32) * scale + _chan_view(coefs[C:], grad_out)
         if residual is not None:
             z = z + residual.to(torch.float32)
-        g = _gate(z, g, negative_slope)
+        g = _gate(z, g, negative_slope, silu)
     dx = (g * scale).to(grad_out.dtype) if want_input_grad else None
     dres = None
     if want_res_grad:

@@ -445,10 +445,13 @@ __global__ void bn_affine_bwd(const float* __restrict__ mean,
 // ACT / RES are compile-time: the fused BN(+add)+ReLU/LeakyReLU epilogue
 // replaces the eager clamp / add kernels and their full-tensor round trips
 // (guide G13: fuse into the producing kernel).  ACT is kActNone / kActRelu /
-// kActLeaky (common.hpp); `slope` is only read by the kActLeaky
-// instantiations, so none / relu keep their arithmetic.
+// kActLeaky / kActSilu (common.hpp); `slope` is only read by the kActLeaky
+// instantiations, so none / relu keep their arithmetic.  kActSilu adds one
+// v_exp_f32 and one v_rcp_f32 per element (quarter rate: ~3.9e13/s over the
+// chip against ~1.3e12 elements/s of memory traffic), so the kernel stays
+// memory-bound.
 //
-// GATE(V = 8, RES, an activation): the thread also stores the byte of gate
+// GATE(V = 8, RES, relu or leaky): the thread also stores the byte of gate
 // bits of its pack (common.hpp), taken from the z it already holds, so the
 // backward reduce can take its branch from the bit and skip the res read.
 // =====================================================================
@@ -459,7 +462,7 @@ __global__ void bn_elemt_nchw(const T* __restrict__ x,
                               const float* __restrict__ shift, int64_t total,
                               int64_t C, int64_t S, float slope,
                               unsigned char* __restrict__ gate_out) {
-  static_assert(!GATE || (V == 8 && RES && ACT != kActNone),
+  static_assert(!GATE || (V == 8 && RES && act_has_gate_bit(ACT)),
                 "gate bits: one byte per 8-pack of a bn+add+act layer");
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -499,7 +502,7 @@ __global__ void bn_elemt_nhwc(const T* __restrict__ x,
                               const float* __restrict__ shift, int64_t total,
                               int64_t C, float slope,
                               unsigned char* __restrict__ gate_out) {
-  static_assert(!GATE || (V == 8 && RES && ACT != kActNone),
+  static_assert(!GATE || (V == 8 && RES && act_has_gate_bit(ACT)),
                 "gate bits: one byte per 8-pack of a bn+add+act layer");
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -535,10 +538,17 @@ __global__ void bn_elemt_nhwc(const T* __restrict__ x,
 
 // =====================================================================
 // backward reduce partial: {sum_g, sum_g*(x-mean)} per channel, where
-// g = dy through the fused activation's gate when ACT (relu: z>0 ? dy : 0,
-// leaky: z>0 ? dy : slope*dy): the pre-activation
+// g = dy through the fused activation's derivative when ACT (relu:
+// z>0 ? dy : 0, leaky: z>0 ? dy : slope*dy, silu: dy*silu'(z), act_grad in
+// common.hpp): the pre-activation
 // z = scale[c]*x + shift[c] (+ res) is recomputed in-kernel, so the fused
 // forward never has to store a mask or the pre-activation tensor.
+//
+// kActSilu: GMOUT stores gm = from_f<T>(g), g rounded to T as for leaky (not
+// exact, unlike relu); the second pass then runs derivative-free on gm, so
+// the sigmoid is evaluated once per element per step on that route.  DY2
+// follows the leaky rule (only with GMOUT, the pair rounded to T once before
+// the derivative).  Never GATE: there is no branch to keep a bit of.
 //
 // DY2: the layer's output forked (residual block: conv1 and the skip path)
 // and the two gradients arrive unsummed; the kernel reads both and folds
@@ -573,7 +583,7 @@ __global__ void bn_bwd_reduce_partial_nchw(const T* __restrict__ dy,
                                            int64_t C, int64_t S, int64_t chunkN,
                                            int64_t chunkS, float slope,
                                            const unsigned char* __restrict__ gate) {
-  static_assert(!GATE || (ACT != kActNone && !RES && GMOUT && V <= 8),
+  static_assert(!GATE || (act_has_gate_bit(ACT) && !RES && GMOUT && V <= 8),
                 "gate bits replace the res read of a gm-writing reduce");
   const int64_t c = blockIdx.x;
   const float m = mean[c];
@@ -598,7 +608,7 @@ __global__ void bn_bwd_reduce_partial_nchw(const T* __restrict__ dy,
         } else if (ACT) {
           float z = sc * xv + sh;
           if (RES) z += to_f(nt_load1(&res[base + s]));
-          g = act_gate<ACT>(z, g, slope);
+          g = act_grad<ACT>(z, g, slope);
         }
         if (GMOUT) nt_store1(&gm_out[base + s], from_f<T>(g));
         acc.add2(g, g * (xv - m));
@@ -626,7 +636,7 @@ __global__ void bn_bwd_reduce_partial_nchw(const T* __restrict__ dy,
           } else if (ACT) {
             float z = sc * xv + sh;
             if (RES) z += to_f(pr.v[k]);
-            g = act_gate<ACT>(z, g, slope);
+            g = act_grad<ACT>(z, g, slope);
           }
           if (GMOUT) pm.v[k] = from_f<T>(g);
           acc.add2(g, g * (xv - m));
@@ -660,7 +670,7 @@ __global__ void bn_bwd_reduce_partial_nchw_flat(
     const float* __restrict__ scale, const float* __restrict__ shift,
     double* __restrict__ ws, int64_t N, int64_t C, int64_t S,
     int64_t chunk_len, float slope, const unsigned char* __restrict__ gate) {
-  static_assert(!GATE || (ACT != kActNone && !RES && GMOUT),
+  static_assert(!GATE || (act_has_gate_bit(ACT) && !RES && GMOUT),
                 "gate bits replace the res read of a gm-writing reduce");
   const int64_t c = blockIdx.x;
   const float m = mean[c];
@@ -682,7 +692,7 @@ __global__ void bn_bwd_reduce_partial_nchw_flat(
     } else if (ACT) {
       float z = sc * xv + sh;
       if (RES) z += to_f(nt_load1(&res[e]));
-      g = act_gate<ACT>(z, g, slope);
+      g = act_grad<ACT>(z, g, slope);
     }
     if (GMOUT) nt_store1(&gm_out[e], from_f<T>(g));
     acc.add2(g, g * (xv - m));
@@ -717,7 +727,7 @@ __global__ void bn_bwd_reduce_partial_nhwc(const T* __restrict__ dy,
                                            int64_t chunk_rows, int lpr,
                                            float slope,
                                            const unsigned char* __restrict__ gate) {
-  static_assert(!GATE || (ACT != kActNone && !RES && GMOUT && V <= 8),
+  static_assert(!GATE || (act_has_gate_bit(ACT) && !RES && GMOUT && V <= 8),
                 "gate bits replace the res read of a gm-writing reduce");
   const int rpi = blockDim.x / lpr;
   const int lane = threadIdx.x % lpr;
@@ -759,7 +769,7 @@ __global__ void bn_bwd_reduce_partial_nhwc(const T* __restrict__ dy,
         } else if (ACT) {
           float z = scv[k] * xv + shv[k];
           if (RES) z += to_f(pr.v[k]);
-          g = act_gate<ACT>(z, g, slope);
+          g = act_grad<ACT>(z, g, slope);
         }
         if (GMOUT) pm.v[k] = from_f<T>(g);
         acc[k].add2(g, g * (xv - m[k]));
@@ -842,7 +852,8 @@ __global__ void bn_bwd_reduce_finalize(const double* __restrict__ ws,
 
 // =====================================================================
 // backward elementwise: dx = a[c]*g + b[c]*x + d[c], with the activation
-// gate recomputed in-kernel when ACT (g = z>0 ? dy : 0 or slope*dy); RESG
+// gate recomputed in-kernel when ACT (g = z>0 ? dy : 0 or slope*dy; silu:
+// g = dy*silu'(z), act_grad); RESG
 // additionally writes the residual-branch gradient dres = g (the add node's
 // pass-through).
 // =====================================================================
@@ -872,7 +883,7 @@ __global__ void bn_bwd_elemt_nchw(const T* __restrict__ dy,
       if (ACT) {
         float z = sc * xv + sh;
         if (RES) z += to_f(nt_load1(&res[e]));
-        g = act_gate<ACT>(z, g, slope);
+        g = act_grad<ACT>(z, g, slope);
       }
       nt_store1(&dx[e], from_f<T>(A * g + B * xv + D));
       if (RESG) nt_store1(&dres[e], from_f<T>(g));
@@ -889,7 +900,7 @@ __global__ void bn_bwd_elemt_nchw(const T* __restrict__ dy,
         if (ACT) {
           float z = sc * xv + sh;
           if (RES) z += to_f(pr.v[k]);
-          g = act_gate<ACT>(z, g, slope);
+          g = act_grad<ACT>(z, g, slope);
         }
         po.v[k] = from_f<T>(A * g + B * xv + D);
         if (RESG) pq.v[k] = from_f<T>(g);
@@ -922,7 +933,7 @@ __global__ void bn_bwd_elemt_nhwc(const T* __restrict__ dy,
       if (ACT) {
         float z = scale[c] * xv + shift[c];
         if (RES) z += to_f(nt_load1(&res[e]));
-        g = act_gate<ACT>(z, g, slope);
+        g = act_grad<ACT>(z, g, slope);
       }
       nt_store1(&dx[e], from_f<T>(ca[c] * g + cb[c] * xv + cd[c]));
       if (RESG) nt_store1(&dres[e], from_f<T>(g));
@@ -947,7 +958,7 @@ __global__ void bn_bwd_elemt_nhwc(const T* __restrict__ dy,
         if (ACT) {
           float z = psc.v[k] * xv + psh.v[k];
           if (RES) z += to_f(pr.v[k]);
-          g = act_gate<ACT>(z, g, slope);
+          g = act_grad<ACT>(z, g, slope);
         }
         po.v[k] = from_f<T>(pa.v[k] * g + pb.v[k] * xv + pd.v[k]);
         if (RESG) pq.v[k] = from_f<T>(g);
@@ -1187,7 +1198,8 @@ __global__ void bn_bwd_elemt_dual_nhwc(const T* __restrict__ gm,
 // batch reduction anywhere.  One tiny kernel folds (running_mean,
 // running_var, eps, weight, bias) into the packed [scale | shift] buffer the
 // forward elemt kernels consume; backward is ONE elementwise pass
-//   dx = scale[c]*g,  dres = g,  g = dy * 1[z > 0]  (leaky: slope*dy else)
+//   dx = scale[c]*g,  dres = g,  g = dy * 1[z > 0]  (leaky: slope*dy else;
+//   silu: g = dy * silu'(z))
 // with the activation gate recomputed from (x, scale, shift[, res]) exactly
 // as bn_bwd_elemt_* does.  Without the gate (kActNone) x is never read, so
 // the layer does not have to keep its input alive.
@@ -1232,7 +1244,7 @@ __global__ void bn_frozen_bwd_elemt_nchw(const T* __restrict__ dy,
       if (ACT) {
         float z = sc * to_f(nt_load1(&x[e])) + sh;
         if (RES) z += to_f(nt_load1(&res[e]));
-        g = act_gate<ACT>(z, g, slope);
+        g = act_grad<ACT>(z, g, slope);
       }
       if (dx != nullptr) nt_store1(&dx[e], from_f<T>(sc * g));
       if (RESG) nt_store1(&dres[e], from_f<T>(g));
@@ -1248,7 +1260,7 @@ __global__ void bn_frozen_bwd_elemt_nchw(const T* __restrict__ dy,
         if (ACT) {
           float z = sc * to_f(px.v[k]) + sh;
           if (RES) z += to_f(pr.v[k]);
-          g = act_gate<ACT>(z, g, slope);
+          g = act_grad<ACT>(z, g, slope);
         }
         po.v[k] = from_f<T>(sc * g);
         if (RESG) pq.v[k] = from_f<T>(g);
@@ -1280,7 +1292,7 @@ __global__ void bn_frozen_bwd_elemt_nhwc(const T* __restrict__ dy,
       if (ACT) {
         float z = sc * to_f(nt_load1(&x[e])) + shift[c];
         if (RES) z += to_f(nt_load1(&res[e]));
-        g = act_gate<ACT>(z, g, slope);
+        g = act_grad<ACT>(z, g, slope);
       }
       if (dx != nullptr) nt_store1(&dx[e], from_f<T>(sc * g));
       if (RESG) nt_store1(&dres[e], from_f<T>(g));
@@ -1301,7 +1313,7 @@ __global__ void bn_frozen_bwd_elemt_nhwc(const T* __restrict__ dy,
         if (ACT) {
           float z = psc.v[k] * to_f(px.v[k]) + psh.v[k];
           if (RES) z += to_f(pr.v[k]);
-          g = act_gate<ACT>(z, g, slope);
+          g = act_grad<ACT>(z, g, slope);
         }
         po.v[k] = from_f<T>(psc.v[k] * g);
         if (RESG) pq.v[k] = from_f<T>(g);
@@ -2853,7 +2865,38 @@ inline int act_mode(bool on, float slope) {
   return !on ? kActNone : (slope == 0.f ? kActRelu : kActLeaky);
 }
 
+// ... and with the ops' `act` argument, which names what (on, slope) cannot:
+// "" is the pair on its own, "silu" -> kActSilu.  The mode is never encoded
+// in the slope.  Only the two-stage and frozen launchers take it; every
+// other family (small-plane, pool, dual, grouped, in-place) has no SiLU
+// kernels and no way to ask for one.
+inline int act_mode(bool on, float slope, const std::string& act,
+                    const char* op) {
+  if (act.empty()) return act_mode(on, slope);
+  TORCH_CHECK(act == "silu", op, ": act must be \"\" or \"silu\", got \"",
+              act, "\"");
+  TORCH_CHECK(on && slope == 0.f, op,
+              ": act=\"silu\" needs the activation flag and a zero "
+              "negative_slope");
+  return kActSilu;
+}
+
+// MSBN_DISPATCH_ACT: every mode, for the families that instantiate SiLU
+// (two-stage elemt / reduce / backward elemt).  MSBN_DISPATCH_ACT_GATED: the
+// three single-bit-gate modes, for the families act_mode(on, slope) feeds.
 #define MSBN_DISPATCH_ACT(MODE, NAME, ...)                                   \
+  [&] {                                                                      \
+    switch (MODE) {                                                          \
+      case kActSilu: {                                                       \
+        constexpr int NAME = kActSilu;                                       \
+        return __VA_ARGS__();                                                \
+      }                                                                      \
+      default:                                                               \
+        return MSBN_DISPATCH_ACT_GATED(MODE, NAME, __VA_ARGS__);             \
+    }                                                                        \
+  }()
+
+#define MSBN_DISPATCH_ACT_GATED(MODE, NAME, ...)                             \
   [&] {                                                                      \
     switch (MODE) {                                                          \
       case kActRelu: {                                                       \
@@ -2894,10 +2937,10 @@ void check_gate_tensor(const at::Tensor& gate, const at::Tensor& input,
               "bytes on the input's device");
 }
 
-// The bit-storing forward kernels exist for an activation, a residual and a
+// The bit-storing forward kernels exist for relu / leaky, a residual and a
 // pack of 8 (one thread = one byte); anything else declines.
 inline bool elemt_writes_gate(int act, bool has_res, int v) {
-  return act != kActNone && has_res && v == 8;
+  return act_has_gate_bit(act) && has_res && v == 8;
 }
 }  // namespace
 
@@ -2907,7 +2950,7 @@ std::tuple<at::Tensor, bool> batch_norm_elemt_act(
     const c10::optional<at::Tensor>& bias, const at::Tensor& mean,
     const at::Tensor& invstd, bool relu,
     const c10::optional<at::Tensor>& coefs_in, double negative_slope,
-    const c10::optional<at::Tensor>& gate_out) {
+    const c10::optional<at::Tensor>& gate_out, const std::string& act_name) {
   const Layout L = get_layout(input);
   auto out = at::empty_like(input);
   if (gate_out.has_value())
@@ -2915,7 +2958,7 @@ std::tuple<at::Tensor, bool> batch_norm_elemt_act(
   bool wrote_gate = false;
   if (input.numel() == 0) return {out, wrote_gate};
   const float slope = (float)negative_slope;
-  const int act = act_mode(relu, slope);
+  const int act = act_mode(relu, slope, act_name, "batch_norm_elemt_act");
   auto stream = cur_stream();
   auto coefs = coefs_in.has_value()
                    ? *coefs_in
@@ -2966,7 +3009,7 @@ std::tuple<at::Tensor, bool> batch_norm_elemt_act(
           // the bit store is compiled for the one combination that can run
           // it (elemt_writes_gate): 2 dtypes x 2 activations x 2 layouts
           constexpr bool kCanGate = VV == 8 && sizeof(native_t) == 2 &&
-                                    ACT_ != kActNone && RES_;
+                                    act_has_gate_bit(ACT_) && RES_;
           if (wrote_gate) {
             launch(std::integral_constant<bool, kCanGate>{});
           } else {
@@ -2987,7 +3030,7 @@ at::Tensor batch_norm_elemt(const at::Tensor& input,
   (void)eps;  // invstd already folds eps
   return std::get<0>(batch_norm_elemt_act(input, c10::nullopt, weight, bias,
                                           mean, invstd, false, c10::nullopt,
-                                          0.0, c10::nullopt));
+                                          0.0, c10::nullopt, ""));
 }
 
 std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor>
@@ -2999,18 +3042,19 @@ batch_norm_backward_reduce_act(
     bool weight_g, bool bias_g, const c10::optional<at::Tensor>& coefs_in,
     const c10::optional<at::Tensor>& gm_out, double negative_slope,
     const c10::optional<at::Tensor>& grad_out2,
-    const c10::optional<at::Tensor>& gate) {
+    const c10::optional<at::Tensor>& gate, const std::string& act_name) {
   const Layout L = get_layout(input);
   const float slope = (float)negative_slope;
-  const int act = act_mode(relu_mask, slope);
+  const int act = act_mode(relu_mask, slope, act_name,
+                           "batch_norm_backward_reduce_act");
   const bool has_gate = gate.has_value();
   if (has_gate) {
-    // the bits stand in for the residual: the forward wrote them for an
-    // activated bn+add layer of a 2-byte dtype, and gm carries the result
-    TORCH_CHECK(act != kActNone && !residual.has_value() &&
+    // the bits stand in for the residual: the forward wrote them for a
+    // relu / leaky bn+add layer of a 2-byte dtype, and gm carries the result
+    TORCH_CHECK(act_has_gate_bit(act) && !residual.has_value() &&
                     gm_out.has_value() && input.element_size() == 2,
-                "gate needs relu_mask, gm_out, a bf16 / half input and no "
-                "residual");
+                "gate needs relu_mask (relu or leaky), gm_out, a bf16 / half "
+                "input and no residual");
     check_gate_tensor(*gate, input, "gate");
   }
   if (input.numel() == 0) {
@@ -3101,12 +3145,13 @@ batch_norm_backward_reduce_act(
         MSBN_DISPATCH_BOOL(want_gm, GM_, [&] {
           // DY2 exists only with GMOUT (has_dy2 implies want_gm, checked
           // above): 3 kernels per (T, V, ACT, RES), not 4
-          // GATE likewise only where the checks above let it run (an
-          // activation, GMOUT, no RES, a 2-byte dtype)
+          // GATE likewise only where the checks above let it run (relu or
+          // leaky, GMOUT, no RES, a 2-byte dtype)
           auto launch = [&](auto dy2_c, auto gate_c) {
             constexpr bool DY2_ = decltype(dy2_c)::value && GM_;
             constexpr bool GATE_ = decltype(gate_c)::value && GM_ && !RES_ &&
-                                   ACT_ != kActNone && sizeof(native_t) == 2;
+                                   act_has_gate_bit(ACT_) &&
+                                   sizeof(native_t) == 2;
             if (!L.nhwc) {
               if (plan.path == RedPath::NchwFlat) {
                 const auto& g = plan.flat;
@@ -3182,7 +3227,7 @@ batch_norm_backward_reduce(const at::Tensor& grad_out, const at::Tensor& input,
                                         invstd, weight, c10::nullopt, false,
                                         input_g, weight_g, bias_g,
                                         c10::nullopt, c10::nullopt, 0.0,
-                                        c10::nullopt, c10::nullopt);
+                                        c10::nullopt, c10::nullopt, "");
 }
 
 std::tuple<at::Tensor, at::Tensor> batch_norm_backward_elemt_act(
@@ -3192,10 +3237,11 @@ std::tuple<at::Tensor, at::Tensor> batch_norm_backward_elemt_act(
     const c10::optional<at::Tensor>& bias, const at::Tensor& sum_dy,
     const at::Tensor& sum_dy_xmu, const at::Tensor& count, bool relu_mask,
     bool want_res_grad, const c10::optional<at::Tensor>& coefs_in,
-    double negative_slope) {
+    double negative_slope, const std::string& act_name) {
   const Layout L = get_layout(input);
   const float slope = (float)negative_slope;
-  const int act = act_mode(relu_mask, slope);
+  const int act = act_mode(relu_mask, slope, act_name,
+                           "batch_norm_backward_elemt_act");
   auto dx = at::empty_like(grad_out);
   at::Tensor dres;
   if (want_res_grad) dres = at::empty_like(grad_out);
@@ -3288,7 +3334,7 @@ at::Tensor batch_norm_backward_elemt(
     const at::Tensor& count) {
   return std::get<0>(batch_norm_backward_elemt_act(
       grad_out, input, c10::nullopt, mean, invstd, weight, c10::nullopt,
-      sum_dy, sum_dy_xmu, count, false, false, c10::nullopt, 0.0));
+      sum_dy, sum_dy_xmu, count, false, false, c10::nullopt, 0.0, ""));
 }
 
 // ---------------------------------------------------------------------------
@@ -3369,7 +3415,7 @@ std::tuple<at::Tensor, at::Tensor> batch_norm_elemt_act_pool(
     MSBN_DISPATCH_V(plan.v, VMAX, [&] {
       // the dispatcher names widths past 16 B for this type; never chosen
       constexpr int VK = VV * (int)sizeof(native_t) <= 16 ? VV : 1;
-      MSBN_DISPATCH_ACT(act, ACT_, [&] {
+      MSBN_DISPATCH_ACT_GATED(act, ACT_, [&] {
         hipLaunchKernelGGL((bn_elemt_pool_nhwc<native_t, VK, ACT_>),
                            dim3(plan.grid), dim3(MSBN_BLOCK), 0, stream, x, y,
                            cp, scale, shift, total, L.C, g.H, g.W, g.OH, g.OW,
@@ -3445,7 +3491,7 @@ batch_norm_backward_reduce_act_pool(
     MSBN_DISPATCH_V(plan.v, VMAX, [&] {
       // the dispatcher names widths past 16 B for this type; never chosen
       constexpr int VK = VV * (int)sizeof(native_t) <= 16 ? VV : 1;
-      MSBN_DISPATCH_ACT(act, ACT_, [&] {
+      MSBN_DISPATCH_ACT_GATED(act, ACT_, [&] {
         MSBN_DISPATCH_BOOL(has_dy2, DY2_, [&] {
           hipLaunchKernelGGL(
               (bn_bwd_reduce_pool_partial_nhwc<native_t, VK, ACT_, DY2_>),
@@ -3547,7 +3593,7 @@ at::Tensor batch_norm_backward_elemt_act_pool(
     MSBN_DISPATCH_V(plan.v, VMAX, [&] {
       // the dispatcher names widths past 16 B for this type; never chosen
       constexpr int VK = VV * (int)sizeof(native_t) <= 16 ? VV : 1;
-      MSBN_DISPATCH_ACT(act, ACT_, [&] {
+      MSBN_DISPATCH_ACT_GATED(act, ACT_, [&] {
         MSBN_DISPATCH_BOOL(has_dy2, DY2_, [&] {
           hipLaunchKernelGGL(
               (bn_bwd_elemt_pool_nhwc<native_t, VK, ACT_, DY2_>),
@@ -3886,8 +3932,10 @@ std::tuple<at::Tensor, at::Tensor> batch_norm_frozen_backward_elemt(
     const at::Tensor& grad_out, const c10::optional<at::Tensor>& input,
     const c10::optional<at::Tensor>& residual, const at::Tensor& coefs,
     bool relu_mask, bool want_input_grad, bool want_res_grad,
-    double negative_slope) {
+    double negative_slope, const std::string& act_name) {
   const float slope = (float)negative_slope;
+  const int act = act_mode(relu_mask, slope, act_name,
+                           "batch_norm_frozen_backward_elemt");
   TORCH_CHECK(grad_out.dim() >= 2,
               "batch_norm_frozen_backward_elemt: grad_out must be >= 2-D");
   const Layout L = get_layout(grad_out);
@@ -3973,9 +4021,10 @@ std::tuple<at::Tensor, at::Tensor> batch_norm_frozen_backward_elemt(
         else if (resg) launch(act_c, F{}, T{});
         else launch(act_c, F{}, F{});
       };
-      if (!relu_mask) launch(ActC<kActNone>{}, F{}, F{});
-      else if (slope == 0.f) gated(ActC<kActRelu>{});
-      else gated(ActC<kActLeaky>{});
+      if (act == kActNone) launch(ActC<kActNone>{}, F{}, F{});
+      else if (act == kActRelu) gated(ActC<kActRelu>{});
+      else if (act == kActLeaky) gated(ActC<kActLeaky>{});
+      else gated(ActC<kActSilu>{});
     });
   });
   return {dx, dres};
@@ -4071,7 +4120,7 @@ batch_norm_fwd_fused_local(const at::Tensor& input,
     constexpr int VMAX = 16 / (int)sizeof(native_t);
     const int v = pick_v((int)sizeof(native_t), {x, res, yp}, S);
     MSBN_DISPATCH_V(v, VMAX, [&] {
-      MSBN_DISPATCH_ACT(act_mode(relu, slope), ACT_, [&] {
+      MSBN_DISPATCH_ACT_GATED(act_mode(relu, slope), ACT_, [&] {
         MSBN_DISPATCH_BOOL(has_res, RES_, [&] {
           hipLaunchKernelGGL(
               (bn_fwd_fused_small_nchw<native_t, VV, ACT_, RES_>),

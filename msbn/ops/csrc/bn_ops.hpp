@@ -86,6 +86,10 @@ at::Tensor batch_norm_backward_elemt(
 // negative_slope generalises the activation to LeakyReLU: forward
 // z>0 ? z : slope*z, gate z>0 ? dy : slope*dy.  It is only consulted when
 // the relu / relu_mask flag is set, and 0.0 runs the plain ReLU kernels.
+// act (trailing, "" by default) names an activation the pair cannot: "silu"
+// is y = z*sigmoid(z), backward g = dy*s*(1 + z*(1 - s)) with s = sigmoid(z)
+// recomputed from z like the gate.  It needs the flag set and a zero slope,
+// has no gate bits, and exists in the two-stage and frozen ops only.
 at::Tensor bn_make_coefs(const at::Tensor& mean, const at::Tensor& invstd,
                          const c10::optional<at::Tensor>& weight,
                          const c10::optional<at::Tensor>& bias);
@@ -102,7 +106,7 @@ std::tuple<at::Tensor, bool> batch_norm_elemt_act(
     const c10::optional<at::Tensor>& bias, const at::Tensor& mean,
     const at::Tensor& invstd, bool relu,
     const c10::optional<at::Tensor>& coefs_in, double negative_slope,
-    const c10::optional<at::Tensor>& gate_out);
+    const c10::optional<at::Tensor>& gate_out, const std::string& act = "");
 
 // grad_out2: second gradient of a forked output (residual block: conv1 and
 // the skip path), delivered unsummed.  The kernel uses
@@ -121,7 +125,7 @@ batch_norm_backward_reduce_act(
     bool weight_g, bool bias_g, const c10::optional<at::Tensor>& coefs_in,
     const c10::optional<at::Tensor>& gm_out, double negative_slope,
     const c10::optional<at::Tensor>& grad_out2,
-    const c10::optional<at::Tensor>& gate);
+    const c10::optional<at::Tensor>& gate, const std::string& act = "");
 
 // ---- frozen path (normalize with running stats, autograd on) --------------
 // One launch: (running_mean, running_var, eps, weight?, bias?) -> packed fp32
@@ -141,7 +145,7 @@ std::tuple<at::Tensor, at::Tensor> batch_norm_frozen_backward_elemt(
     const at::Tensor& grad_out, const c10::optional<at::Tensor>& input,
     const c10::optional<at::Tensor>& residual, const at::Tensor& coefs,
     bool relu_mask, bool want_input_grad, bool want_res_grad,
-    double negative_slope);
+    double negative_slope, const std::string& act = "");
 
 // ---- small-plane world-1 fused path (single launch fwd / bwd) -------------
 // Stock K10-style block-per-channel kernels gated to small NCHW planes
@@ -182,7 +186,7 @@ std::tuple<at::Tensor, at::Tensor> batch_norm_backward_elemt_act(
     const c10::optional<at::Tensor>& bias, const at::Tensor& sum_dy,
     const at::Tensor& sum_dy_xmu, const at::Tensor& count, bool relu_mask,
     bool want_res_grad, const c10::optional<at::Tensor>& coefs_in,
-    double negative_slope);
+    double negative_slope, const std::string& act = "");
 
 // ---- stem pool fusion: bn + act + MaxPool2d(3, 2, 1) -----------------------
 // Channels-last 4-D input only; the pool geometry is fixed (kernel 3,

@@ -55,12 +55,38 @@ __device__ __forceinline__ __half from_f<__half>(float x) {
 constexpr int kActNone = 0;
 constexpr int kActRelu = 1;
 constexpr int kActLeaky = 2;
+// SiLU, z * sigmoid(z).  It has no branch, so nothing below that speaks of a
+// gate (act_pass, act_gate_bit, gate bits) exists for it: the backward needs
+// act'(z) as a value and gets it from act_grad.  `slope` is never read.
+constexpr int kActSilu = 3;
+
+// The modes whose backward is one predicate per element, i.e. the only ones
+// a gate-bit kernel may be instantiated or launched for.
+constexpr bool act_has_gate_bit(int act) {
+  return act == kActRelu || act == kActLeaky;
+}
+
+// sigmoid(z) = 1 / (1 + exp(-z)) on the hardware transcendentals: one
+// v_exp_f32 (exp(-z) = 2^(-z*log2(e))) and one v_rcp_f32, each good to 1 ulp.
+// The product -z*log2(e) is rounded before the exponential, which costs
+// exp(-z) a relative |z| * 6e-8; sigmoid sees that error scaled by
+// (1 - sigmoid), so z*sigmoid(z) is off by at most z^2 * sigmoid *
+// (1 - sigmoid) * 6e-8 < 3e-8 absolute at any z (the factor peaks at 0.44
+// near |z| = 2.4), a fraction of an fp32 ulp of the result there.
+// Saturation needs no branch: for z <~ -88.7 the exponential overflows to
+// +inf, 1 + inf = inf and rcp(inf) = +0; for z >~ 88 it underflows to 0 (or
+// a flushed denormal) and rcp(1) = 1.  A NaN z stays NaN through both.
+__device__ __forceinline__ float fast_sigmoid(float z) {
+  constexpr float kLog2e = 1.4426950408889634f;
+  return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-z * kLog2e));
+}
 
 // forward: y = act(z)
 template <int ACT>
 __device__ __forceinline__ float act_fwd(float z, float slope) {
   if (ACT == kActRelu) return fmaxf(z, 0.f);
   if (ACT == kActLeaky) return z > 0.f ? z : slope * z;
+  if (ACT == kActSilu) return z * fast_sigmoid(z);
   return z;
 }
 
@@ -92,6 +118,23 @@ __device__ __forceinline__ float act_gate_bit(bool pass, float g,
 template <int ACT>
 __device__ __forceinline__ float act_gate(float z, float g, float slope) {
   return act_gate_bit<ACT>(act_pass<ACT>(z), g, slope);
+}
+
+// backward of every recomputing kernel: g = dy * act'(z).  none / relu /
+// leaky ARE act_gate (same code, so their arithmetic cannot move); SiLU is
+//   act'(z) = s * (1 + z * (1 - s)),  s = sigmoid(z)
+// in fp32.  1 - s is formed by subtraction, not as exp(-z)*s: that product is
+// inf * 0 = NaN once the exponential has overflowed, and the subtraction's
+// 6e-8 absolute error only matters multiplied by |z| < 17 (beyond it s
+// itself is 1 or 1 - s exact to its last bit).  At z <~ -88.7 s = +0 and
+// g = dy * 0; at z >~ 17 g = dy * (1 + z * tiny): finite for finite input.
+template <int ACT>
+__device__ __forceinline__ float act_grad(float z, float g, float slope) {
+  if (ACT == kActSilu) {
+    const float s = fast_sigmoid(z);
+    return g * (s * (1.f + z * (1.f - s)));
+  }
+  return act_gate<ACT>(z, g, slope);
 }
 
 // ------------------------------------------------------------------ gate bits

@@ -48,7 +48,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("residual"), py::arg("weight"), py::arg("bias"),
         py::arg("mean"), py::arg("invstd"), py::arg("relu"),
         py::arg("coefs") = py::none(), py::arg("negative_slope") = 0.0,
-        py::arg("gate_out") = py::none());
+        py::arg("gate_out") = py::none(), py::arg("act") = "");
   m.def("batch_norm_backward_reduce_act",
         &msbn::batch_norm_backward_reduce_act, py::arg("grad_out"),
         py::arg("input"), py::arg("residual"), py::arg("mean"),
@@ -56,13 +56,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("relu_mask"), py::arg("input_g"), py::arg("weight_g"),
         py::arg("bias_g"), py::arg("coefs") = py::none(),
         py::arg("gm_out") = py::none(), py::arg("negative_slope") = 0.0,
-        py::arg("grad_out2") = py::none(), py::arg("gate") = py::none());
+        py::arg("grad_out2") = py::none(), py::arg("gate") = py::none(),
+        py::arg("act") = "");
   m.def("batch_norm_backward_elemt_act", &msbn::batch_norm_backward_elemt_act,
         py::arg("grad_out"), py::arg("input"), py::arg("residual"),
         py::arg("mean"), py::arg("invstd"), py::arg("weight"), py::arg("bias"),
         py::arg("sum_dy"), py::arg("sum_dy_xmu"), py::arg("count"),
         py::arg("relu_mask"), py::arg("want_res_grad"),
-        py::arg("coefs") = py::none(), py::arg("negative_slope") = 0.0);
+        py::arg("coefs") = py::none(), py::arg("negative_slope") = 0.0,
+        py::arg("act") = "");
 
   m.def("batch_norm_elemt_act_pool", &msbn::batch_norm_elemt_act_pool,
         py::arg("input"), py::arg("weight"), py::arg("bias"), py::arg("mean"),
@@ -160,7 +162,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         &msbn::batch_norm_frozen_backward_elemt, py::arg("grad_out"),
         py::arg("input"), py::arg("residual"), py::arg("coefs"),
         py::arg("relu_mask"), py::arg("want_input_grad"),
-        py::arg("want_res_grad"), py::arg("negative_slope") = 0.0);
+        py::arg("want_res_grad"), py::arg("negative_slope") = 0.0,
+        py::arg("act") = "");
 
   m.def("bn_fused_local_eligible", &msbn::bn_fused_local_eligible,
         py::arg("input"), py::arg("weight"), py::arg("bias"),
