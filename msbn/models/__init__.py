@@ -1,6 +1,7 @@
 from msbn.models.simple import SimpleCNN  # noqa: F401
 from msbn.models.resnet import resnet18, resnet50, ResNet  # noqa: F401
 from msbn.models.dcgan import Generator, Discriminator  # noqa: F401
+from msbn.models.mbconv import MBConv, MBConvNet, mbconv_net  # noqa: F401
 # imported up front: importing the submodule binds the package attribute
 # ``retinanet`` to it, and the factory below has to be the last binding
 from msbn.models.retinanet import RetinaNet  # noqa: F401
@@ -12,6 +13,9 @@ __all__ = [
     "ResNet",
     "Generator",
     "Discriminator",
+    "MBConv",
+    "MBConvNet",
+    "mbconv_net",
 ]
 
 

@@ -1,0 +1,86 @@
+"""MBConv (inverted residual) blocks, the unit of EfficientNet / MobileNetV2
+style backbones, with this project's BatchNorm+SiLU layers:
+
+    1x1 expand -> BN+SiLU -> depthwise 3x3 (stride 1 | 2) -> BN+SiLU ->
+    1x1 project -> BN (+ identity skip where the shapes allow)
+
+No squeeze-excite.  ``conv_stats=True`` runs the two 1x1 convolutions
+through ``conv1x1_bn_act`` and the depthwise one through ``dwconv3x3_bn_act``:
+the convolution kernels then emit the following BatchNorm's statistics and
+its statistics pass does not run.  Whatever those routes do not take runs the
+composition, so the flag changes neither modules nor state-dict keys.
+"""
+
+from typing import Sequence
+
+import torch.nn as nn
+
+from msbn.nn import SyncBatchNorm
+from msbn.nn.fused import (SyncBatchNormAct2d, conv1x1_bn_act,
+                           dwconv3x3_bn_act)
+
+
+def _bn_silu(channels):
+    return SyncBatchNormAct2d(channels, act="silu")
+
+
+class MBConv(nn.Module):
+    def __init__(self, cin: int, cout: int, stride: int = 1, expand: int = 4,
+                 conv_stats: bool = False):
+        super().__init__()
+        if stride not in (1, 2):
+            raise ValueError("MBConv: stride must be 1 or 2")
+        mid = cin * expand
+        self.conv_stats = conv_stats
+        self.skip = stride == 1 and cin == cout
+        self.conv1 = nn.Conv2d(cin, mid, 1, bias=False)
+        self.bn1 = _bn_silu(mid)
+        self.conv2 = nn.Conv2d(mid, mid, 3, stride, 1, groups=mid, bias=False)
+        self.bn2 = _bn_silu(mid)
+        self.conv3 = nn.Conv2d(mid, cout, 1, bias=False)
+        self.bn3 = SyncBatchNorm(cout)
+
+    def forward(self, x):
+        if self.conv_stats:
+            out = conv1x1_bn_act(self.conv1, self.bn1, x)
+            out = dwconv3x3_bn_act(self.conv2, self.bn2, out)
+            out = conv1x1_bn_act(self.conv3, self.bn3, out)
+        else:
+            out = self.bn1(self.conv1(x))
+            out = self.bn2(self.conv2(out))
+            out = self.bn3(self.conv3(out))
+        return out + x if self.skip else out
+
+
+class MBConvNet(nn.Module):
+    def __init__(self, widths: Sequence[int], depths: Sequence[int],
+                 num_classes: int = 1000, expand: int = 4,
+                 conv_stats: bool = False):
+        super().__init__()
+        if len(widths) != len(depths) or not widths:
+            raise ValueError("mbconv_net: one depth per width")
+        self.stem = nn.Conv2d(3, widths[0], 3, 2, 1, bias=False)
+        self.stem_bn = _bn_silu(widths[0])
+        blocks, cin = [], widths[0]
+        for i, (width, depth) in enumerate(zip(widths, depths)):
+            for j in range(depth):
+                stride = 2 if j == 0 and i > 0 else 1
+                blocks.append(MBConv(cin, width, stride, expand, conv_stats))
+                cin = width
+        self.blocks = nn.Sequential(*blocks)
+        self.pool = nn.AdaptiveAvgPool2d(1)
+        self.fc = nn.Linear(cin, num_classes)
+
+    def forward(self, x):
+        x = self.blocks(self.stem_bn(self.stem(x)))
+        return self.fc(self.pool(x).flatten(1))
+
+
+def mbconv_net(widths: Sequence[int] = (16, 24, 40, 80, 112, 192),
+               depths: Sequence[int] = (1, 2, 2, 3, 3, 4),
+               num_classes: int = 1000, expand: int = 4,
+               conv_stats: bool = False) -> MBConvNet:
+    """A stack of MBConv stages (stage i > 0 opens with a stride-2 block)
+    behind a plain 3x3/2 stem, with a pooled linear head.  The defaults are
+    EfficientNet-B0's widths and depths up to its 192-channel stage."""
+    return MBConvNet(widths, depths, num_classes, expand, conv_stats)

@@ -901,6 +901,86 @@ def conv1x1_bn_act(conv, bn, x: torch.Tensor,
     return _bn_call(bn, y, residual, fork, partials)
 
 
+class DwConv3x3StatsFunction(torch.autograd.Function):
+    """A depthwise 3x3 convolution (padding 1, stride 1 or 2) through
+    ``ops.dwconv3x3_stats``: returns ``(y, partials)`` as
+    ``Conv1x1StatsFunction`` does.  The backward is the stock convolution
+    backward on the saved ``(x, weight)`` with ``groups = C``.  Callers check
+    that the op takes the tensors (``dwconv_stats_eligible``)."""
+
+    @staticmethod
+    def forward(ctx, x: torch.Tensor, weight: torch.Tensor, stride: int):
+        y, partials, _ = ops.dwconv3x3_stats(x, weight, stride)
+        if y is None:
+            raise RuntimeError(
+                "dwconv3x3_stats declined tensors its plan takes")
+        ctx.save_for_backward(x, weight)
+        ctx.stride = stride
+        ctx.mark_non_differentiable(partials)
+        return y, partials
+
+    @staticmethod
+    def backward(ctx, grad_y, _grad_partials=None):
+        x, weight = ctx.saved_tensors
+        s = ctx.stride
+        mask = [ctx.needs_input_grad[0], ctx.needs_input_grad[1], False]
+        dx, dw, _ = torch.ops.aten.convolution_backward(
+            grad_y, x, weight, None, [s, s], [1, 1], [1, 1], False, [0, 0],
+            x.shape[1], mask,
+        )
+        return (dx if mask[0] else None), (dw if mask[1] else None), None
+
+
+def _dwconv_kind(stride: int) -> str:
+    return "dwconv3x3_stats" if stride == 1 else "dwconv3x3s2_stats"
+
+
+def dwconv_stats_eligible(conv, bn, x: torch.Tensor) -> bool:
+    """True when ``bn(conv(x))`` can run as dwconv3x3_stats + finalize: an
+    ``nn.Conv2d`` proper that is 3x3, padding 1 (zeros), undilated, stride
+    (1, 1) or (2, 2), depthwise with multiplier 1 (``groups == in_channels ==
+    out_channels``), bias-free and hook-free, a BatchNorm that
+    ``_takes_partials``, autocast off, and tensors the kernel takes
+    (``ops.dwconv3x3_stats``)."""
+    if not (
+        type(conv) is torch.nn.Conv2d and conv.bias is None
+        and _pair(conv.kernel_size) == (3, 3)
+        and _pair(conv.stride) in ((1, 1), (2, 2))
+        and conv.padding_mode == "zeros" and not isinstance(conv.padding, str)
+        and _pair(conv.padding) == (1, 1) and _pair(conv.dilation) == (1, 1)
+        and conv.groups == conv.in_channels == conv.out_channels
+        and not _hooked(conv) and _takes_partials(bn)
+        and x.is_cuda and x.dim() == 4 and not torch.is_autocast_enabled()
+    ):
+        return False
+    plan = ops.launch_plan(_dwconv_kind(_pair(conv.stride)[0]), x,
+                           (conv.weight,))
+    return plan["path"] == "dwconv"
+
+
+def dwconv3x3_with_stats(conv, bn, x: torch.Tensor):
+    """``(conv(x), partials)``: through ``DwConv3x3StatsFunction`` where
+    ``dwconv_stats_eligible``, else the module's own convolution and None."""
+    if dwconv_stats_eligible(conv, bn, x):
+        return DwConv3x3StatsFunction.apply(x, conv.weight,
+                                            _pair(conv.stride)[0])
+    return conv(x), None
+
+
+def dwconv3x3_bn_act(conv, bn, x: torch.Tensor,
+                     residual: Optional[torch.Tensor] = None,
+                     fork: bool = False):
+    """``bn(conv(x), residual=residual, fork=fork)`` for a depthwise 3x3
+    convolution and the BatchNorm after it.  Where ``dwconv_stats_eligible``
+    the convolution runs as this project's streaming kernel, which forms the
+    BatchNorm's statistics from the values it stores: the statistics pass
+    over the conv output does not run.  The output then differs from the
+    composition's by the convolution's accumulation order (both accumulate in
+    fp32 and round once).  Anything else is exactly the composition."""
+    y, partials = dwconv3x3_with_stats(conv, bn, x)
+    return _bn_call(bn, y, residual, fork, partials)
+
+
 def bn_add_bn_act(bn, bn_skip, x: torch.Tensor, x_skip: torch.Tensor,
                   fork: bool = False, *, partials=None, partials_skip=None):
     """``bn(x, residual=bn_skip(x_skip), fork=fork)`` for the closing

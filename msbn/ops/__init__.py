@@ -556,6 +556,33 @@ def conv1x1_stats(input: torch.Tensor, weight: torch.Tensor):
     return y, partials, int(nchunks)
 
 
+def dwconv3x3_stats(input: torch.Tensor, weight: torch.Tensor,
+                    stride: int = 1):
+    """A depthwise 3x3 convolution (padding 1, dilation 1, ``stride`` 1 or 2
+    in both dimensions, ``groups == Cin == Cout``, no bias) as one streaming
+    kernel that also forms the statistics of the BatchNorm that follows it
+    (docs/KERNEL_DESIGN.md "Depthwise conv + statistics").
+
+    Returns ``(y, partials, nchunks)`` as ``conv1x1_stats`` does: ``y``
+    channels-last ``[N, C, OH, OW]`` with ``OH = (H - 1) // stride + 1``,
+    accumulated in fp32 (``kh`` then ``kw`` ascending) and rounded to the
+    input dtype once; ``partials`` the fp64 ``[C][nchunks][2]`` workspace of
+    ``{sum y, sum y^2}`` over the rounded values.
+
+    Returns ``(None, None, 0)`` and launches nothing for what the kernel
+    does not take: anything but a non-empty dense channels-last 4-D bf16 /
+    half GPU input with a contiguous ``[C, 1, 3, 3]`` weight of the same
+    dtype and device, ``C`` a multiple of 8, 16-byte aligned pointers and a
+    stride of 1 or 2.  The caller then runs the convolution it has."""
+    if not input.is_cuda or not weight.is_cuda:
+        return None, None, 0
+    y, partials, nchunks = _require_hip().dwconv3x3_stats(
+        input, weight, int(stride))
+    if y is None:
+        return None, None, 0
+    return y, partials, int(nchunks)
+
+
 def batch_norm_stats_local_from_partials(partials, nchunks: int, count: int,
                                          eps: float, running_mean,
                                          running_var, momentum: float,
@@ -690,6 +717,13 @@ def launch_plan(kind: str, input: torch.Tensor, others=(), coefs=None) -> dict:
     ``tiles_per_block`` (most row tiles one block visits), ``k_trips`` and
     ``lds_bytes``, or ``"ineligible"`` where the op declines (the device is
     not looked at: the plan of a CPU tensor is that of its GPU copy).
+      ``"dwconv3x3_stats"``   input = x, others = (weight,)   (stride 1)
+      ``"dwconv3x3s2_stats"`` input = x, others = (weight,)   (stride 2)
+    They report path ``"dwconv"`` with ``V``, ``lpr`` (lanes across the
+    channels), ``ctiles``, ``strip`` (output columns of a work item),
+    ``items`` (work items), ``chunk_items``, ``nchunks``, ``trips`` (the most
+    items one thread visits), ``flush_every`` and ``finalize_trips``, or
+    ``"ineligible"`` where ``dwconv3x3_stats`` declines.
     ``None`` entries of ``others`` are absent tensors.  The dual kinds
     report path ``"nhwc"`` with their single counterparts' numbers plus
     ``dual: True``, or ``"ineligible"`` where the dual kernels decline.
@@ -737,6 +771,7 @@ __all__ = [
     "launch_plan",
     "gate_bits_empty",
     "conv1x1_stats",
+    "dwconv3x3_stats",
     "batch_norm_stats_local_from_partials",
     "batch_norm_stats_packed_from_partials",
     "batch_norm_stats_local_grouped",

@@ -4517,6 +4517,25 @@ std::tuple<std::string, std::map<std::string, int64_t>> launch_plan(
     return {"mfma", d};
   }
 
+  // depthwise 3x3 conv + statistics: others = {weight}
+  if (kind == "dwconv3x3_stats" || kind == "dwconv3x3s2_stats") {
+    if (!given(0)) return {"ineligible", d};
+    const DwConvPlan p =
+        dwconv3x3_plan(input, *others[0], kind == "dwconv3x3_stats" ? 1 : 2);
+    if (!p.ok) return {"ineligible", d};
+    d["V"] = p.v;
+    d["lpr"] = p.lpr;
+    d["ctiles"] = p.ctiles;
+    d["strip"] = p.strip;
+    d["items"] = p.items;
+    d["chunk_items"] = p.chunk_items;
+    d["nchunks"] = p.nchunks;
+    d["trips"] = p.trips;
+    d["flush_every"] = p.flush_every;
+    d["finalize_trips"] = cdiv(p.nchunks, MSBN_WAVE);
+    return {"dwconv", d};
+  }
+
   // dual BN: the single counterparts' numbers plus "dual", or "ineligible"
   // where the ops decline and the composition runs
   if (kind == "elemt_dual" || kind == "bwd_elemt_dual") {

@@ -331,6 +331,40 @@ struct Conv1x1Plan {
 };
 Conv1x1Plan conv1x1_plan(const at::Tensor& input, const at::Tensor& weight);
 
+// ---- depthwise 3x3 conv + statistics (dwconv_stats_kernels.hip) ------------
+// y[n, c, oh, ow] = sum_{kh, kw} x[n, c, oh*s - 1 + kh, ow*s - 1 + kw] *
+// w[c, 0, kh, kw]: kernel 3x3, padding 1, dilation 1, stride s in {1, 2},
+// groups == Cin == Cout, no bias, OH = (H - 1)/s + 1, OW = (W - 1)/s + 1.
+// Products and sums in fp32, kh then kw ascending into one accumulator,
+// rounded to the input dtype once; the statistics are those of the rounded
+// values.  Returns (y, partials, nchunks) as conv1x1_stats does.
+//
+// Declines -- (undefined, undefined, 0), nothing launched -- for anything
+// but a non-empty dense channels-last 4-D bf16 / half GPU input with a
+// contiguous [C, 1, 3, 3] weight of the same dtype and device, C a multiple
+// of 8, 16-byte aligned pointers and a stride of 1 or 2.
+std::tuple<at::Tensor, at::Tensor, int64_t> dwconv3x3_stats(
+    const at::Tensor& input, const at::Tensor& weight, int64_t stride);
+
+// The launch dwconv3x3_stats would make (device not considered); ok == false
+// where it declines.
+struct DwConvPlan {
+  bool ok;
+  int64_t n, c, h, w, oh, ow;
+  int stride;
+  int v;                // channels of a lane
+  int lpr;              // lanes across the channel axis
+  int ctiles;           // grid.x
+  int strip;            // output columns of a work item
+  int64_t items;        // work items: N * OH * ceil(OW / strip)
+  int64_t chunk_items;  // items of a chunk (block)
+  int nchunks;          // grid.y = partials per channel
+  int trips;            // most items one thread visits
+  int flush_every;      // most fp32 terms between two flushes
+};
+DwConvPlan dwconv3x3_plan(const at::Tensor& input, const at::Tensor& weight,
+                          int64_t stride);
+
 // batch_norm_stats_local / batch_norm_stats_packed with the partial stage
 // already done: they run bn_stats_finalize alone over `partials`
 // (fp64 [C][nchunks][2] of {sum x, sum x^2}, `count` elements per channel)
@@ -438,6 +472,11 @@ std::tuple<std::string, std::map<std::string, int64_t>> launch_plan_grouped(
 //   "conv1x1_stats"      input = x,      others = {weight}: path "mfma" with
 //                        nchunks, row_tile, slab, nslabs, tiles_per_block,
 //                        k_trips and lds_bytes, or "ineligible"
+//   "dwconv3x3_stats" (stride 1) / "dwconv3x3s2_stats" (stride 2)
+//                        input = x,      others = {weight}: path "dwconv" with
+//                        V, lpr, ctiles, strip, items, chunk_items, nchunks,
+//                        trips, flush_every and finalize_trips, or
+//                        "ineligible"
 //   "stats_grouped" / "elemt_grouped"          input = x_0, others = {x_1 ..
 //                        x_{S-1}}; "bwd_reduce_grouped" / "bwd_elemt_grouped"
 //                        others = {x_1 .. x_{S-1}, dy_0 .. dy_{S-1}}: path

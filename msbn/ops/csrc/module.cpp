@@ -122,6 +122,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
 
   m.def("conv1x1_stats", &msbn::conv1x1_stats, py::arg("input"),
         py::arg("weight"));
+  m.def("dwconv3x3_stats", &msbn::dwconv3x3_stats, py::arg("input"),
+        py::arg("weight"), py::arg("stride") = 1);
   m.def("batch_norm_stats_local_from_partials",
         &msbn::batch_norm_stats_local_from_partials, py::arg("partials"),
         py::arg("nchunks"), py::arg("count"), py::arg("eps"),
