@@ -9,6 +9,9 @@ through ``conv1x1_bn_act`` and the depthwise one through ``dwconv3x3_bn_act``:
 the convolution kernels then emit the following BatchNorm's statistics and
 its statistics pass does not run.  Whatever those routes do not take runs the
 composition, so the flag changes neither modules nor state-dict keys.
+``dw_grad=True`` also runs the depthwise convolution's backward as this
+project's gradient kernels (``ops.dwconv3x3_backward``); it is honoured only
+where ``conv_stats=True``.
 """
 
 from typing import Sequence
@@ -26,12 +29,13 @@ def _bn_silu(channels):
 
 class MBConv(nn.Module):
     def __init__(self, cin: int, cout: int, stride: int = 1, expand: int = 4,
-                 conv_stats: bool = False):
+                 conv_stats: bool = False, dw_grad: bool = False):
         super().__init__()
         if stride not in (1, 2):
             raise ValueError("MBConv: stride must be 1 or 2")
         mid = cin * expand
         self.conv_stats = conv_stats
+        self.dw_grad = dw_grad  # honoured only where conv_stats
         self.skip = stride == 1 and cin == cout
         self.conv1 = nn.Conv2d(cin, mid, 1, bias=False)
         self.bn1 = _bn_silu(mid)
@@ -43,7 +47,8 @@ class MBConv(nn.Module):
     def forward(self, x):
         if self.conv_stats:
             out = conv1x1_bn_act(self.conv1, self.bn1, x)
-            out = dwconv3x3_bn_act(self.conv2, self.bn2, out)
+            out = dwconv3x3_bn_act(self.conv2, self.bn2, out,
+                                   grad_kernels=self.dw_grad)
             out = conv1x1_bn_act(self.conv3, self.bn3, out)
         else:
             out = self.bn1(self.conv1(x))
@@ -55,7 +60,7 @@ class MBConv(nn.Module):
 class MBConvNet(nn.Module):
     def __init__(self, widths: Sequence[int], depths: Sequence[int],
                  num_classes: int = 1000, expand: int = 4,
-                 conv_stats: bool = False):
+                 conv_stats: bool = False, dw_grad: bool = False):
         super().__init__()
         if len(widths) != len(depths) or not widths:
             raise ValueError("mbconv_net: one depth per width")
@@ -65,7 +70,8 @@ class MBConvNet(nn.Module):
         for i, (width, depth) in enumerate(zip(widths, depths)):
             for j in range(depth):
                 stride = 2 if j == 0 and i > 0 else 1
-                blocks.append(MBConv(cin, width, stride, expand, conv_stats))
+                blocks.append(MBConv(cin, width, stride, expand, conv_stats,
+                                     dw_grad))
                 cin = width
         self.blocks = nn.Sequential(*blocks)
         self.pool = nn.AdaptiveAvgPool2d(1)
@@ -79,8 +85,12 @@ class MBConvNet(nn.Module):
 def mbconv_net(widths: Sequence[int] = (16, 24, 40, 80, 112, 192),
                depths: Sequence[int] = (1, 2, 2, 3, 3, 4),
                num_classes: int = 1000, expand: int = 4,
-               conv_stats: bool = False) -> MBConvNet:
+               conv_stats: bool = False, dw_grad: bool = False) -> MBConvNet:
     """A stack of MBConv stages (stage i > 0 opens with a stride-2 block)
     behind a plain 3x3/2 stem, with a pooled linear head.  The defaults are
-    EfficientNet-B0's widths and depths up to its 192-channel stage."""
-    return MBConvNet(widths, depths, num_classes, expand, conv_stats)
+    EfficientNet-B0's widths and depths up to its 192-channel stage.
+    ``dw_grad=True`` runs the depthwise convolutions' backward as this
+    project's gradient kernels; it is honoured only where
+    ``conv_stats=True``."""
+    return MBConvNet(widths, depths, num_classes, expand, conv_stats,
+                     dw_grad)

@@ -906,16 +906,22 @@ class DwConv3x3StatsFunction(torch.autograd.Function):
     ``ops.dwconv3x3_stats``: returns ``(y, partials)`` as
     ``Conv1x1StatsFunction`` does.  The backward is the stock convolution
     backward on the saved ``(x, weight)`` with ``groups = C``.  Callers check
-    that the op takes the tensors (``dwconv_stats_eligible``)."""
+    that the op takes the tensors (``dwconv_stats_eligible``).
+
+    ``grad_kernels=True``: the backward asks ``ops.dwconv3x3_backward`` for
+    the gradients it needs and runs the stock backward only for what comes
+    back ``None`` (a ``grad_y`` the kernels decline)."""
 
     @staticmethod
-    def forward(ctx, x: torch.Tensor, weight: torch.Tensor, stride: int):
+    def forward(ctx, x: torch.Tensor, weight: torch.Tensor, stride: int,
+                grad_kernels: bool = False):
         y, partials, _ = ops.dwconv3x3_stats(x, weight, stride)
         if y is None:
             raise RuntimeError(
                 "dwconv3x3_stats declined tensors its plan takes")
         ctx.save_for_backward(x, weight)
         ctx.stride = stride
+        ctx.grad_kernels = grad_kernels
         ctx.mark_non_differentiable(partials)
         return y, partials
 
@@ -924,11 +930,24 @@ class DwConv3x3StatsFunction(torch.autograd.Function):
         x, weight = ctx.saved_tensors
         s = ctx.stride
         mask = [ctx.needs_input_grad[0], ctx.needs_input_grad[1], False]
+        if ctx.grad_kernels:
+            dx, dw = ops.dwconv3x3_backward(grad_y, x, weight, s, mask[0],
+                                            mask[1])
+            mask = [mask[0] and dx is None, mask[1] and dw is None, False]
+            if not (mask[0] or mask[1]):
+                return dx, dw, None, None
+            sdx, sdw, _ = torch.ops.aten.convolution_backward(
+                grad_y, x, weight, None, [s, s], [1, 1], [1, 1], False,
+                [0, 0], x.shape[1], mask,
+            )
+            return (sdx if mask[0] else dx), (sdw if mask[1] else dw), \
+                None, None
         dx, dw, _ = torch.ops.aten.convolution_backward(
             grad_y, x, weight, None, [s, s], [1, 1], [1, 1], False, [0, 0],
             x.shape[1], mask,
         )
-        return (dx if mask[0] else None), (dw if mask[1] else None), None
+        return (dx if mask[0] else None), (dw if mask[1] else None), None, \
+            None
 
 
 def _dwconv_kind(stride: int) -> str:
@@ -958,26 +977,33 @@ def dwconv_stats_eligible(conv, bn, x: torch.Tensor) -> bool:
     return plan["path"] == "dwconv"
 
 
-def dwconv3x3_with_stats(conv, bn, x: torch.Tensor):
+def dwconv3x3_with_stats(conv, bn, x: torch.Tensor,
+                         grad_kernels: bool = False):
     """``(conv(x), partials)``: through ``DwConv3x3StatsFunction`` where
     ``dwconv_stats_eligible``, else the module's own convolution and None."""
     if dwconv_stats_eligible(conv, bn, x):
         return DwConv3x3StatsFunction.apply(x, conv.weight,
-                                            _pair(conv.stride)[0])
+                                            _pair(conv.stride)[0],
+                                            grad_kernels)
     return conv(x), None
 
 
 def dwconv3x3_bn_act(conv, bn, x: torch.Tensor,
                      residual: Optional[torch.Tensor] = None,
-                     fork: bool = False):
+                     fork: bool = False, *, grad_kernels: bool = False):
     """``bn(conv(x), residual=residual, fork=fork)`` for a depthwise 3x3
     convolution and the BatchNorm after it.  Where ``dwconv_stats_eligible``
     the convolution runs as this project's streaming kernel, which forms the
     BatchNorm's statistics from the values it stores: the statistics pass
     over the conv output does not run.  The output then differs from the
     composition's by the convolution's accumulation order (both accumulate in
-    fp32 and round once).  Anything else is exactly the composition."""
-    y, partials = dwconv3x3_with_stats(conv, bn, x)
+    fp32 and round once).  Anything else is exactly the composition.
+
+    ``grad_kernels=True`` also runs that convolution's backward through
+    ``ops.dwconv3x3_backward`` (both gradients as this project's kernels;
+    the stock backward for whatever they decline).  It has no effect where
+    the composition runs."""
+    y, partials = dwconv3x3_with_stats(conv, bn, x, grad_kernels)
     return _bn_call(bn, y, residual, fork, partials)
 
 

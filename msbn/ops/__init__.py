@@ -583,6 +583,32 @@ def dwconv3x3_stats(input: torch.Tensor, weight: torch.Tensor,
     return y, partials, int(nchunks)
 
 
+def dwconv3x3_backward(grad_y: torch.Tensor, input: torch.Tensor,
+                       weight: torch.Tensor, stride: int = 1,
+                       want_dx: bool = True, want_dw: bool = True):
+    """Both gradients of the depthwise 3x3 convolution ``dwconv3x3_stats``
+    computes, as streaming kernels of this project (docs/KERNEL_DESIGN.md
+    "Depthwise conv gradients").
+
+    Returns ``(dx, dw)``, each ``None`` where not wanted.  ``dx`` is
+    channels-last like ``input``: per element the taps inside ``grad_y`` in
+    fp32, ``grad_y`` rows then columns ascending into one accumulator, rounded
+    to the input dtype once.  ``dw`` is a contiguous ``[C, 1, 3, 3]``: fp32
+    products summed for at most 64 terms, then in fp64 through a
+    deterministic two-stage reduction, rounded once.
+
+    Returns ``(None, None)`` and launches nothing for what the kernels do not
+    take: everything ``dwconv3x3_stats`` declines, and a ``grad_y`` that is
+    not a dense channels-last ``[N, C, OH, OW]`` of the input's dtype and
+    device at a 16-byte aligned address.  Always ``(None, None)`` for CPU
+    tensors.  The caller then runs the convolution backward it has."""
+    if not (input.is_cuda and weight.is_cuda and grad_y.is_cuda):
+        return None, None
+    dx, dw = _require_hip().dwconv3x3_backward(
+        grad_y, input, weight, int(stride), bool(want_dx), bool(want_dw))
+    return dx, dw
+
+
 def batch_norm_stats_local_from_partials(partials, nchunks: int, count: int,
                                          eps: float, running_mean,
                                          running_var, momentum: float,
@@ -724,6 +750,14 @@ def launch_plan(kind: str, input: torch.Tensor, others=(), coefs=None) -> dict:
     ``items`` (work items), ``chunk_items``, ``nchunks``, ``trips`` (the most
     items one thread visits), ``flush_every`` and ``finalize_trips``, or
     ``"ineligible"`` where ``dwconv3x3_stats`` declines.
+      ``"dwconv3x3_dgrad"`` / ``"dwconv3x3_wgrad"``      (stride 1)
+      ``"dwconv3x3s2_dgrad"`` / ``"dwconv3x3s2_wgrad"``  (stride 2)
+                              input = x, others = (weight, grad_y)
+    The launches of ``dwconv3x3_backward``: path ``"dwconv"`` with the same
+    numbers (``items`` are strips of ``dx`` for dgrad and of ``grad_y`` for
+    wgrad, whose ``trips * strip <= flush_every`` holds by construction;
+    ``finalize_trips`` for wgrad alone), or ``"ineligible"`` where the op
+    declines.
     ``None`` entries of ``others`` are absent tensors.  The dual kinds
     report path ``"nhwc"`` with their single counterparts' numbers plus
     ``dual: True``, or ``"ineligible"`` where the dual kernels decline.
@@ -772,6 +806,7 @@ __all__ = [
     "gate_bits_empty",
     "conv1x1_stats",
     "dwconv3x3_stats",
+    "dwconv3x3_backward",
     "batch_norm_stats_local_from_partials",
     "batch_norm_stats_packed_from_partials",
     "batch_norm_stats_local_grouped",

@@ -4536,6 +4536,29 @@ std::tuple<std::string, std::map<std::string, int64_t>> launch_plan(
     return {"dwconv", d};
   }
 
+  // depthwise 3x3 conv gradients: others = {weight, grad_y}
+  if (kind == "dwconv3x3_dgrad" || kind == "dwconv3x3s2_dgrad" ||
+      kind == "dwconv3x3_wgrad" || kind == "dwconv3x3s2_wgrad") {
+    if (!given(0) || !given(1)) return {"ineligible", d};
+    const bool wgrad = kind.find("wgrad") != std::string::npos;
+    const int64_t stride = kind.find("s2_") != std::string::npos ? 2 : 1;
+    const DwConvPlan p =
+        wgrad ? dwconv3x3_wgrad_plan(input, *others[0], *others[1], stride)
+              : dwconv3x3_dgrad_plan(input, *others[0], *others[1], stride);
+    if (!p.ok) return {"ineligible", d};
+    d["V"] = p.v;
+    d["lpr"] = p.lpr;
+    d["ctiles"] = p.ctiles;
+    d["strip"] = p.strip;
+    d["items"] = p.items;
+    d["chunk_items"] = p.chunk_items;
+    d["nchunks"] = p.nchunks;
+    d["trips"] = p.trips;
+    d["flush_every"] = p.flush_every;
+    if (wgrad) d["finalize_trips"] = cdiv(p.nchunks, MSBN_WAVE);
+    return {"dwconv", d};
+  }
+
   // dual BN: the single counterparts' numbers plus "dual", or "ineligible"
   // where the ops decline and the composition runs
   if (kind == "elemt_dual" || kind == "bwd_elemt_dual") {

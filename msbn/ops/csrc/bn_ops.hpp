@@ -365,6 +365,37 @@ struct DwConvPlan {
 DwConvPlan dwconv3x3_plan(const at::Tensor& input, const at::Tensor& weight,
                           int64_t stride);
 
+// ---- depthwise 3x3 conv gradients (dwconv_grad_kernels.hip) ---------------
+// Both gradients of the convolution above from grad_y [N, C, OH, OW]:
+//   dx[n,c,ih,iw] = sum dy[n,c,oh,ow] * w[c,0,kh,kw] over the taps with
+//                   ih = oh*s - 1 + kh, iw = ow*s - 1 + kw inside dy
+//   dw[c,0,kh,kw] = sum over (n,oh,ow) dy[n,c,oh,ow] * x[n,c,oh*s-1+kh,
+//                   ow*s-1+kw] inside x
+// dx: fp32 products and sums, dy rows then dy columns ascending into one
+// accumulator, rounded once, channels-last like x.  dw: at most
+// MSBN_ACC_FLUSH fp32 terms per accumulator, then fp64 (a deterministic
+// two-stage reduction, no atomics), rounded once, contiguous [C, 1, 3, 3].
+// Returns (dx, dw), each undefined where not wanted.
+//
+// Declines -- (undefined, undefined), nothing launched -- for whatever
+// dwconv3x3_stats declines and for a grad_y that is not a dense channels-last
+// [N, C, OH, OW] of the input's dtype and device at a 16-byte aligned address.
+std::tuple<at::Tensor, at::Tensor> dwconv3x3_backward(
+    const at::Tensor& grad_y, const at::Tensor& input,
+    const at::Tensor& weight, int64_t stride, bool want_dx, bool want_dw);
+
+// The launches dwconv3x3_backward would make (device not considered), in
+// DwConvPlan's terms.  dgrad: items = N * H * ceil(W / strip) dx strips,
+// flush_every = 9 (the taps of an element).  wgrad: items = N * OH *
+// ceil(OW / strip) dy strips, nchunks = partials per (channel, tap), and
+// trips * strip <= flush_every = MSBN_ACC_FLUSH by construction.
+DwConvPlan dwconv3x3_dgrad_plan(const at::Tensor& input,
+                                const at::Tensor& weight,
+                                const at::Tensor& grad_y, int64_t stride);
+DwConvPlan dwconv3x3_wgrad_plan(const at::Tensor& input,
+                                const at::Tensor& weight,
+                                const at::Tensor& grad_y, int64_t stride);
+
 // batch_norm_stats_local / batch_norm_stats_packed with the partial stage
 // already done: they run bn_stats_finalize alone over `partials`
 // (fp64 [C][nchunks][2] of {sum x, sum x^2}, `count` elements per channel)
@@ -477,6 +508,11 @@ std::tuple<std::string, std::map<std::string, int64_t>> launch_plan_grouped(
 //                        V, lpr, ctiles, strip, items, chunk_items, nchunks,
 //                        trips, flush_every and finalize_trips, or
 //                        "ineligible"
+//   "dwconv3x3_dgrad" / "dwconv3x3_wgrad" (stride 1), "dwconv3x3s2_dgrad" /
+//   "dwconv3x3s2_wgrad" (stride 2)
+//                        input = x,      others = {weight, grad_y}: path
+//                        "dwconv" with the same numbers (finalize_trips for
+//                        wgrad alone), or "ineligible"
 //   "stats_grouped" / "elemt_grouped"          input = x_0, others = {x_1 ..
 //                        x_{S-1}}; "bwd_reduce_grouped" / "bwd_elemt_grouped"
 //                        others = {x_1 .. x_{S-1}, dy_0 .. dy_{S-1}}: path

@@ -124,6 +124,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("weight"));
   m.def("dwconv3x3_stats", &msbn::dwconv3x3_stats, py::arg("input"),
         py::arg("weight"), py::arg("stride") = 1);
+  m.def("dwconv3x3_backward", &msbn::dwconv3x3_backward, py::arg("grad_y"),
+        py::arg("input"), py::arg("weight"), py::arg("stride"),
+        py::arg("want_dx"), py::arg("want_dw"));
   m.def("batch_norm_stats_local_from_partials",
         &msbn::batch_norm_stats_local_from_partials, py::arg("partials"),
         py::arg("nchunks"), py::arg("count"), py::arg("eps"),
