@@ -835,6 +835,8 @@ def conv_stats_eligible(conv, bn, x: torch.Tensor) -> bool:
         and _pair(conv.padding) == (0, 0) and _pair(conv.dilation) == (1, 1)
         and conv.groups == 1 and not _hooked(conv) and _takes_partials(bn)
         and x.is_cuda and x.dim() == 4 and not torch.is_autocast_enabled()
+        # an empty rank (the join() shadow step) has no plan to ask for
+        and x.numel() > 0
     ):
         return False
     plan = ops.launch_plan("conv1x1_stats", x, (conv.weight,))
@@ -970,6 +972,8 @@ def dwconv_stats_eligible(conv, bn, x: torch.Tensor) -> bool:
         and conv.groups == conv.in_channels == conv.out_channels
         and not _hooked(conv) and _takes_partials(bn)
         and x.is_cuda and x.dim() == 4 and not torch.is_autocast_enabled()
+        # an empty rank (the join() shadow step) has no plan to ask for
+        and x.numel() > 0
     ):
         return False
     plan = ops.launch_plan(_dwconv_kind(_pair(conv.stride)[0]), x,

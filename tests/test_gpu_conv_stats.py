@@ -221,15 +221,21 @@ class _Stored(torch.autograd.Function):
 def _layer_reference(x, w, res, gamma, beta, x_d, w_d, gamma_d, beta_d, g):
     """float64: relu(bn(conv(x)) + (res | bn_d(conv_d(x_d)))), the tensors
     between the operations rounded to the layer's dtype as it stores them.
-    Returns the outputs / gradients by name and the gradient mask."""
+    Returns the outputs / gradients by name and the gradient mask;
+    ``conv_x`` / ``dconv_x`` are the stored conv output and the gradient
+    that reaches the convolution (what a rank-local gradient is made of)."""
     dt = x.dtype
     leaves = {k: v.detach().cpu().double().requires_grad_(True)
               for k, v in dict(x=x, w=w, res=res, gamma=gamma, beta=beta,
                                x_d=x_d, w_d=w_d, gamma_d=gamma_d,
                                beta_d=beta_d).items() if v is not None}
+    convs = {}
 
     def bn(t, gm, bt, tag):
-        y = _Stored.apply(F.conv2d(leaves[t], leaves[tag]), dt)
+        convs[t] = F.conv2d(leaves[t], leaves[tag])
+        convs[t].retain_grad()
+        y = _Stored.apply(convs[t], dt)
+        out[f"conv_{t}"] = y.detach()
         mean, var, _ = o64.stats(y.detach(), EPS)
         out[f"rm_{t}"] = 0.1 * mean
         out[f"rv_{t}"] = 0.9 + 0.1 * var * (y.numel() // y.shape[1]) / (
@@ -248,6 +254,7 @@ def _layer_reference(x, w, res, gamma, beta, x_d, w_d, gamma_d, beta_d, g):
     y.backward((g * keep).cpu().double())
     out["y"] = y.detach()
     out.update({"d" + k: v.grad for k, v in leaves.items()})
+    out.update({"dconv_" + k: v.grad for k, v in convs.items()})
     return out, keep
 
 

@@ -164,6 +164,31 @@ def test_declined_inputs_run_the_composition(kind, monkeypatch):
     assert torch.equal(bn.running_var, ref_bn.running_var)
 
 
+def _layer_reference(x, w, gamma, beta, stride, act, gout):
+    """float64: silu?(bn(dwconv(x))) from fresh running statistics, the conv
+    output rounded to x's dtype forward and backward.  Outputs / gradients by
+    name; ``conv`` / ``dconv`` / ``dz`` are the stored conv output, the
+    gradient that reaches the convolution and the one that reaches the
+    BatchNorm's output (what a rank-local gradient is made of)."""
+    c = x.shape[1]
+    lv = {k: v.detach().cpu().double().requires_grad_(True) for k, v in
+          dict(x=x, w=w, gamma=gamma, beta=beta).items()}
+    raw = F.conv2d(lv["x"], lv["w"], stride=stride, padding=1, groups=c)
+    raw.retain_grad()
+    yc = cs._Stored.apply(raw, x.dtype)
+    mean, var, _ = o64.stats(yc.detach(), EPS)
+    count = yc.numel() // c
+    z = F.batch_norm(yc, None, None, lv["gamma"], lv["beta"], True, 0.0, EPS)
+    z.retain_grad()
+    want_y = F.silu(z) if act else z
+    want_y.backward(gout.cpu().double())
+    return {"y": want_y.detach(), "dx": lv["x"].grad, "dw": lv["w"].grad,
+            "dgamma": lv["gamma"].grad, "dbeta": lv["beta"].grad,
+            "running_mean": 0.1 * mean,
+            "running_var": 0.9 + 0.1 * var * count / (count - 1.0),
+            "conv": yc.detach(), "dconv": raw.grad, "dz": z.grad}
+
+
 def _run_layer(act, stride, dtype, monkeypatch):
     g = torch.Generator(device=DEV).manual_seed(11 + stride)
     c, shape = 24, (3, 24, 7, 9)
@@ -190,20 +215,8 @@ def _run_layer(act, stride, dtype, monkeypatch):
     gout = rn(*y.shape).to(dtype)
     y.backward(gout)
 
-    # float64, the conv output rounded to dtype forward and backward
-    lv = {k: v.detach().cpu().double().requires_grad_(True) for k, v in
-          dict(x=x, w=conv.weight, gamma=bn.weight, beta=bn.bias).items()}
-    yc = cs._Stored.apply(F.conv2d(lv["x"], lv["w"], stride=stride, padding=1,
-                                   groups=c), dtype)
-    mean, var, _ = o64.stats(yc.detach(), EPS)
-    count = yc.numel() // c
-    z = F.batch_norm(yc, None, None, lv["gamma"], lv["beta"], True, 0.0, EPS)
-    want_y = F.silu(z) if act else z
-    want_y.backward(gout.cpu().double())
-    want = {"y": want_y.detach(), "dx": lv["x"].grad, "dw": lv["w"].grad,
-            "dgamma": lv["gamma"].grad, "dbeta": lv["beta"].grad,
-            "running_mean": 0.1 * mean,
-            "running_var": 0.9 + 0.1 * var * count / (count - 1.0)}
+    want = _layer_reference(x, conv.weight, bn.weight, bn.bias, stride, act,
+                            gout)
     got = {"y": y, "dx": x.grad, "dw": conv.weight.grad,
            "dgamma": bn.weight.grad, "dbeta": bn.bias.grad,
            "running_mean": bn.running_mean, "running_var": bn.running_var}

@@ -90,6 +90,24 @@ def _coef_bounds(mean, var, w, b):
     return scale, shift, scale_b, shift_b
 
 
+def _running_chain(rm0, rv0, stats, counts, momentum=MOM):
+    """(want_mean, want_var, bound_mean, bound_var) of the running statistics
+    after one update per segment, in order, from each segment's float64
+    (mean, var, ...) and element count: the S single-update bounds summed."""
+    want_m, want_v = rm0.double(), rv0.double()
+    bound_m = bound_v = 0.0
+    for (m64, v64, *_), n in zip(stats, counts):
+        rtol, matol = edges._stat_bounds(m64, v64)
+        unb = v64 * (n / (n - 1.0))
+        bound_m = bound_m + momentum * matol + 4 * U * (
+            (1 - momentum) * want_m.abs() + momentum * m64.abs())
+        bound_v = bound_v + momentum * 2 * rtol * (unb + EPS) + 4 * U * (
+            (1 - momentum) * want_v.abs() + momentum * unb)
+        want_m, want_v = o64.running_update(want_m, want_v, m64, v64, n,
+                                            momentum)
+    return want_m, want_v, bound_m, bound_v
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("name", list(GROUPS))
 def test_statistics_and_outputs(name, dtype):
@@ -103,20 +121,13 @@ def test_statistics_and_outputs(name, dtype):
         xs, EPS, rm, rv, MOM, w, b)
     ys = ops.batch_norm_elemt_act_grouped(xs, coefs, True)
     assert mean.shape == invstd.shape == (S, C) and coefs.shape == (S, 2 * C)
-    want_m, want_v = rm0.double(), rv0.double()
-    bound_m = bound_v = 0.0
+    want_m, want_v, bound_m, bound_v = _running_chain(
+        rm0, rv0, stats, [x.numel() // C for x in xs])
     for s, (x, (m64, v64, _)) in enumerate(zip(xs, stats)):
         n = x.numel() // C
         assert count[s].item() == n >= 2
         edges._check_stats(f"seg{s}", mean[s], invstd[s], m64, v64)
         edges._check_coefs(f"seg{s}", coefs[s], m64, v64, w, b)
-        rtol, matol = edges._stat_bounds(m64, v64)
-        unb = v64 * (n / (n - 1.0))
-        bound_m = bound_m + MOM * matol + 4 * U * (
-            (1 - MOM) * want_m.abs() + MOM * m64.abs())
-        bound_v = bound_v + MOM * 2 * rtol * (unb + EPS) + 4 * U * (
-            (1 - MOM) * want_v.abs() + MOM * unb)
-        want_m, want_v = o64.running_update(want_m, want_v, m64, v64, n, MOM)
         scale, shift, scale_b, shift_b = _coef_bounds(m64, v64, w, b)
         xd, ch = x.double(), lambda t: o64.chan(t, 4)
         ref = torch.relu(xd * ch(scale) + ch(shift))
