@@ -1,26 +1,27 @@
 """MBConv (inverted residual) blocks, the unit of EfficientNet / MobileNetV2
 style backbones, with this project's BatchNorm+SiLU layers:
 
-    1x1 expand -> BN+SiLU -> depthwise 3x3 (stride 1 | 2) -> BN+SiLU ->
+    1x1 expand -> BN+SiLU -> depthwise 3x3 | 5x5 (stride 1 | 2) -> BN+SiLU ->
     1x1 project -> BN (+ identity skip where the shapes allow)
 
 No squeeze-excite.  ``conv_stats=True`` runs the two 1x1 convolutions
-through ``conv1x1_bn_act`` and the depthwise one through ``dwconv3x3_bn_act``:
+through ``conv1x1_bn_act`` and the depthwise one through ``dwconv3x3_bn_act``
+or, at kernel size 5, ``dwconv5x5_bn_act``:
 the convolution kernels then emit the following BatchNorm's statistics and
 its statistics pass does not run.  Whatever those routes do not take runs the
 composition, so the flag changes neither modules nor state-dict keys.
 ``dw_grad=True`` also runs the depthwise convolution's backward as this
-project's gradient kernels (``ops.dwconv3x3_backward``); it is honoured only
-where ``conv_stats=True``.
+project's gradient kernels (``ops.dwconv3x3_backward`` /
+``ops.dwconv5x5_backward``); it is honoured only where ``conv_stats=True``.
 """
 
-from typing import Sequence
+from typing import Optional, Sequence
 
 import torch.nn as nn
 
 from msbn.nn import SyncBatchNorm
 from msbn.nn.fused import (SyncBatchNormAct2d, conv1x1_bn_act,
-                           dwconv3x3_bn_act)
+                           dwconv3x3_bn_act, dwconv5x5_bn_act)
 
 
 def _bn_silu(channels):
@@ -29,17 +30,23 @@ def _bn_silu(channels):
 
 class MBConv(nn.Module):
     def __init__(self, cin: int, cout: int, stride: int = 1, expand: int = 4,
-                 conv_stats: bool = False, dw_grad: bool = False):
+                 conv_stats: bool = False, dw_grad: bool = False,
+                 kernel_size: int = 3):
         super().__init__()
         if stride not in (1, 2):
             raise ValueError("MBConv: stride must be 1 or 2")
+        if kernel_size not in (3, 5):
+            raise ValueError("MBConv: kernel_size must be 3 or 5")
         mid = cin * expand
         self.conv_stats = conv_stats
         self.dw_grad = dw_grad  # honoured only where conv_stats
         self.skip = stride == 1 and cin == cout
         self.conv1 = nn.Conv2d(cin, mid, 1, bias=False)
         self.bn1 = _bn_silu(mid)
-        self.conv2 = nn.Conv2d(mid, mid, 3, stride, 1, groups=mid, bias=False)
+        self.conv2 = nn.Conv2d(mid, mid, kernel_size, stride,
+                               kernel_size // 2, groups=mid, bias=False)
+        self._dw_bn_act = dwconv3x3_bn_act if kernel_size == 3 else \
+            dwconv5x5_bn_act
         self.bn2 = _bn_silu(mid)
         self.conv3 = nn.Conv2d(mid, cout, 1, bias=False)
         self.bn3 = SyncBatchNorm(cout)
@@ -47,8 +54,8 @@ class MBConv(nn.Module):
     def forward(self, x):
         if self.conv_stats:
             out = conv1x1_bn_act(self.conv1, self.bn1, x)
-            out = dwconv3x3_bn_act(self.conv2, self.bn2, out,
-                                   grad_kernels=self.dw_grad)
+            out = self._dw_bn_act(self.conv2, self.bn2, out,
+                                  grad_kernels=self.dw_grad)
             out = conv1x1_bn_act(self.conv3, self.bn3, out)
         else:
             out = self.bn1(self.conv1(x))
@@ -60,18 +67,24 @@ class MBConv(nn.Module):
 class MBConvNet(nn.Module):
     def __init__(self, widths: Sequence[int], depths: Sequence[int],
                  num_classes: int = 1000, expand: int = 4,
-                 conv_stats: bool = False, dw_grad: bool = False):
+                 conv_stats: bool = False, dw_grad: bool = False,
+                 kernel_sizes: Optional[Sequence[int]] = None):
         super().__init__()
         if len(widths) != len(depths) or not widths:
             raise ValueError("mbconv_net: one depth per width")
+        if kernel_sizes is None:
+            kernel_sizes = (3,) * len(widths)
+        if len(kernel_sizes) != len(widths):
+            raise ValueError("mbconv_net: one kernel size per width")
         self.stem = nn.Conv2d(3, widths[0], 3, 2, 1, bias=False)
         self.stem_bn = _bn_silu(widths[0])
         blocks, cin = [], widths[0]
-        for i, (width, depth) in enumerate(zip(widths, depths)):
+        for i, (width, depth, ksize) in enumerate(
+                zip(widths, depths, kernel_sizes)):
             for j in range(depth):
                 stride = 2 if j == 0 and i > 0 else 1
                 blocks.append(MBConv(cin, width, stride, expand, conv_stats,
-                                     dw_grad))
+                                     dw_grad, ksize))
                 cin = width
         self.blocks = nn.Sequential(*blocks)
         self.pool = nn.AdaptiveAvgPool2d(1)
@@ -85,12 +98,15 @@ class MBConvNet(nn.Module):
 def mbconv_net(widths: Sequence[int] = (16, 24, 40, 80, 112, 192),
                depths: Sequence[int] = (1, 2, 2, 3, 3, 4),
                num_classes: int = 1000, expand: int = 4,
-               conv_stats: bool = False, dw_grad: bool = False) -> MBConvNet:
+               conv_stats: bool = False, dw_grad: bool = False,
+               kernel_sizes: Optional[Sequence[int]] = None) -> MBConvNet:
     """A stack of MBConv stages (stage i > 0 opens with a stride-2 block)
     behind a plain 3x3/2 stem, with a pooled linear head.  The defaults are
     EfficientNet-B0's widths and depths up to its 192-channel stage.
     ``dw_grad=True`` runs the depthwise convolutions' backward as this
     project's gradient kernels; it is honoured only where
-    ``conv_stats=True``."""
+    ``conv_stats=True``.  ``kernel_sizes`` gives each stage's depthwise
+    kernel size, 3 or 5 (``None``: 3 everywhere); EfficientNet-B0's are
+    ``(3, 3, 5, 3, 5, 5)`` for the default widths."""
     return MBConvNet(widths, depths, num_classes, expand, conv_stats,
-                     dw_grad)
+                     dw_grad, kernel_sizes)

@@ -903,6 +903,40 @@ def conv1x1_bn_act(conv, bn, x: torch.Tensor,
     return _bn_call(bn, y, residual, fork, partials)
 
 
+def _dwconv_stats_forward(ctx, k: int, x, weight, stride, grad_kernels):
+    """The forward both depthwise Functions share; ``k`` is the kernel size."""
+    y, partials, _ = getattr(ops, f"dwconv{k}x{k}_stats")(x, weight, stride)
+    if y is None:
+        raise RuntimeError(
+            f"dwconv{k}x{k}_stats declined tensors its plan takes")
+    ctx.save_for_backward(x, weight)
+    ctx.stride = stride
+    ctx.grad_kernels = grad_kernels
+    ctx.mark_non_differentiable(partials)
+    return y, partials
+
+
+def _dwconv_stats_backward(ctx, k: int, grad_y):
+    """The backward both depthwise Functions share: the project's gradient
+    kernels where ``grad_kernels``, the stock convolution backward (padding
+    ``k // 2``, ``groups = C``) for the rest."""
+    x, weight = ctx.saved_tensors
+    s, pad = ctx.stride, k // 2
+    mask = [ctx.needs_input_grad[0], ctx.needs_input_grad[1], False]
+    dx = dw = None
+    if ctx.grad_kernels:
+        dx, dw = getattr(ops, f"dwconv{k}x{k}_backward")(
+            grad_y, x, weight, s, mask[0], mask[1])
+        mask = [mask[0] and dx is None, mask[1] and dw is None, False]
+        if not (mask[0] or mask[1]):
+            return dx, dw, None, None
+    sdx, sdw, _ = torch.ops.aten.convolution_backward(
+        grad_y, x, weight, None, [s, s], [pad, pad], [1, 1], False, [0, 0],
+        x.shape[1], mask,
+    )
+    return (sdx if mask[0] else dx), (sdw if mask[1] else dw), None, None
+
+
 class DwConv3x3StatsFunction(torch.autograd.Function):
     """A depthwise 3x3 convolution (padding 1, stride 1 or 2) through
     ``ops.dwconv3x3_stats``: returns ``(y, partials)`` as
@@ -917,43 +951,51 @@ class DwConv3x3StatsFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x: torch.Tensor, weight: torch.Tensor, stride: int,
                 grad_kernels: bool = False):
-        y, partials, _ = ops.dwconv3x3_stats(x, weight, stride)
-        if y is None:
-            raise RuntimeError(
-                "dwconv3x3_stats declined tensors its plan takes")
-        ctx.save_for_backward(x, weight)
-        ctx.stride = stride
-        ctx.grad_kernels = grad_kernels
-        ctx.mark_non_differentiable(partials)
-        return y, partials
+        return _dwconv_stats_forward(ctx, 3, x, weight, stride, grad_kernels)
 
     @staticmethod
     def backward(ctx, grad_y, _grad_partials=None):
-        x, weight = ctx.saved_tensors
-        s = ctx.stride
-        mask = [ctx.needs_input_grad[0], ctx.needs_input_grad[1], False]
-        if ctx.grad_kernels:
-            dx, dw = ops.dwconv3x3_backward(grad_y, x, weight, s, mask[0],
-                                            mask[1])
-            mask = [mask[0] and dx is None, mask[1] and dw is None, False]
-            if not (mask[0] or mask[1]):
-                return dx, dw, None, None
-            sdx, sdw, _ = torch.ops.aten.convolution_backward(
-                grad_y, x, weight, None, [s, s], [1, 1], [1, 1], False,
-                [0, 0], x.shape[1], mask,
-            )
-            return (sdx if mask[0] else dx), (sdw if mask[1] else dw), \
-                None, None
-        dx, dw, _ = torch.ops.aten.convolution_backward(
-            grad_y, x, weight, None, [s, s], [1, 1], [1, 1], False, [0, 0],
-            x.shape[1], mask,
-        )
-        return (dx if mask[0] else None), (dw if mask[1] else None), None, \
-            None
+        return _dwconv_stats_backward(ctx, 3, grad_y)
 
 
-def _dwconv_kind(stride: int) -> str:
-    return "dwconv3x3_stats" if stride == 1 else "dwconv3x3s2_stats"
+class DwConv5x5StatsFunction(torch.autograd.Function):
+    """``DwConv3x3StatsFunction`` for a depthwise 5x5 convolution (padding
+    2): ``ops.dwconv5x5_stats`` forward, ``ops.dwconv5x5_backward`` where
+    ``grad_kernels``, the stock backward with padding ``[2, 2]`` for whatever
+    comes back ``None``.  Callers check ``dwconv5x5_stats_eligible``."""
+
+    @staticmethod
+    def forward(ctx, x: torch.Tensor, weight: torch.Tensor, stride: int,
+                grad_kernels: bool = False):
+        return _dwconv_stats_forward(ctx, 5, x, weight, stride, grad_kernels)
+
+    @staticmethod
+    def backward(ctx, grad_y, _grad_partials=None):
+        return _dwconv_stats_backward(ctx, 5, grad_y)
+
+
+def _dwconv_kind(stride: int, k: int = 3) -> str:
+    return f"dwconv{k}x{k}_stats" if stride == 1 else f"dwconv{k}x{k}s2_stats"
+
+
+def _dwconv_eligible(conv, bn, x: torch.Tensor, k: int) -> bool:
+    if not (
+        type(conv) is torch.nn.Conv2d and conv.bias is None
+        and _pair(conv.kernel_size) == (k, k)
+        and _pair(conv.stride) in ((1, 1), (2, 2))
+        and conv.padding_mode == "zeros" and not isinstance(conv.padding, str)
+        and _pair(conv.padding) == (k // 2, k // 2)
+        and _pair(conv.dilation) == (1, 1)
+        and conv.groups == conv.in_channels == conv.out_channels
+        and not _hooked(conv) and _takes_partials(bn)
+        and x.is_cuda and x.dim() == 4 and not torch.is_autocast_enabled()
+        # an empty rank (the join() shadow step) has no plan to ask for
+        and x.numel() > 0
+    ):
+        return False
+    plan = ops.launch_plan(_dwconv_kind(_pair(conv.stride)[0], k), x,
+                           (conv.weight,))
+    return plan["path"] == "dwconv"
 
 
 def dwconv_stats_eligible(conv, bn, x: torch.Tensor) -> bool:
@@ -963,22 +1005,13 @@ def dwconv_stats_eligible(conv, bn, x: torch.Tensor) -> bool:
     out_channels``), bias-free and hook-free, a BatchNorm that
     ``_takes_partials``, autocast off, and tensors the kernel takes
     (``ops.dwconv3x3_stats``)."""
-    if not (
-        type(conv) is torch.nn.Conv2d and conv.bias is None
-        and _pair(conv.kernel_size) == (3, 3)
-        and _pair(conv.stride) in ((1, 1), (2, 2))
-        and conv.padding_mode == "zeros" and not isinstance(conv.padding, str)
-        and _pair(conv.padding) == (1, 1) and _pair(conv.dilation) == (1, 1)
-        and conv.groups == conv.in_channels == conv.out_channels
-        and not _hooked(conv) and _takes_partials(bn)
-        and x.is_cuda and x.dim() == 4 and not torch.is_autocast_enabled()
-        # an empty rank (the join() shadow step) has no plan to ask for
-        and x.numel() > 0
-    ):
-        return False
-    plan = ops.launch_plan(_dwconv_kind(_pair(conv.stride)[0]), x,
-                           (conv.weight,))
-    return plan["path"] == "dwconv"
+    return _dwconv_eligible(conv, bn, x, 3)
+
+
+def dwconv5x5_stats_eligible(conv, bn, x: torch.Tensor) -> bool:
+    """``dwconv_stats_eligible`` for a 5x5 kernel with padding 2 and
+    ``ops.dwconv5x5_stats``."""
+    return _dwconv_eligible(conv, bn, x, 5)
 
 
 def dwconv3x3_with_stats(conv, bn, x: torch.Tensor,
@@ -1008,6 +1041,21 @@ def dwconv3x3_bn_act(conv, bn, x: torch.Tensor,
     the stock backward for whatever they decline).  It has no effect where
     the composition runs."""
     y, partials = dwconv3x3_with_stats(conv, bn, x, grad_kernels)
+    return _bn_call(bn, y, residual, fork, partials)
+
+
+def dwconv5x5_bn_act(conv, bn, x: torch.Tensor,
+                     residual: Optional[torch.Tensor] = None,
+                     fork: bool = False, *, grad_kernels: bool = False):
+    """``dwconv3x3_bn_act`` for a depthwise 5x5 convolution (padding 2):
+    ``ops.dwconv5x5_stats`` where ``dwconv5x5_stats_eligible``, with
+    ``grad_kernels=True`` its backward through ``ops.dwconv5x5_backward``;
+    exactly the composition otherwise."""
+    if dwconv5x5_stats_eligible(conv, bn, x):
+        y, partials = DwConv5x5StatsFunction.apply(
+            x, conv.weight, _pair(conv.stride)[0], grad_kernels)
+    else:
+        y, partials = conv(x), None
     return _bn_call(bn, y, residual, fork, partials)
 
 

@@ -609,6 +609,40 @@ def dwconv3x3_backward(grad_y: torch.Tensor, input: torch.Tensor,
     return dx, dw
 
 
+def dwconv5x5_stats(input: torch.Tensor, weight: torch.Tensor,
+                    stride: int = 1):
+    """``dwconv3x3_stats`` at kernel 5x5, padding 2 (docs/KERNEL_DESIGN.md
+    "Depthwise 5x5"): the input tile goes through LDS once, each thread holds
+    a strip of fp32 accumulators.  ``(y, partials, nchunks)`` with the same
+    arithmetic rules (fp32, ``kh`` then ``kw`` ascending, rounded once,
+    statistics of the rounded values), and ``(None, None, 0)`` with nothing
+    launched for what ``dwconv3x3_stats`` declines, the weight being a
+    contiguous ``[C, 1, 5, 5]``."""
+    if not input.is_cuda or not weight.is_cuda:
+        return None, None, 0
+    y, partials, nchunks = _require_hip().dwconv5x5_stats(
+        input, weight, int(stride))
+    if y is None:
+        return None, None, 0
+    return y, partials, int(nchunks)
+
+
+def dwconv5x5_backward(grad_y: torch.Tensor, input: torch.Tensor,
+                       weight: torch.Tensor, stride: int = 1,
+                       want_dx: bool = True, want_dw: bool = True):
+    """``dwconv3x3_backward`` at kernel 5x5, padding 2: ``(dx, dw)``, each
+    ``None`` where not wanted, ``dw`` a contiguous ``[C, 1, 5, 5]``, under the
+    3x3 op's rules (``dx``: ``grad_y`` rows then columns ascending in fp32,
+    rounded once; ``dw``: at most 64 fp32 terms, then fp64, deterministic,
+    rounded once).  ``(None, None)`` with nothing launched for what the
+    kernels do not take, and always for CPU tensors."""
+    if not (input.is_cuda and weight.is_cuda and grad_y.is_cuda):
+        return None, None
+    dx, dw = _require_hip().dwconv5x5_backward(
+        grad_y, input, weight, int(stride), bool(want_dx), bool(want_dw))
+    return dx, dw
+
+
 def batch_norm_stats_local_from_partials(partials, nchunks: int, count: int,
                                          eps: float, running_mean,
                                          running_var, momentum: float,
@@ -758,6 +792,15 @@ def launch_plan(kind: str, input: torch.Tensor, others=(), coefs=None) -> dict:
     wgrad, whose ``trips * strip <= flush_every`` holds by construction;
     ``finalize_trips`` for wgrad alone), or ``"ineligible"`` where the op
     declines.
+      ``"dwconv5x5_stats"`` / ``"dwconv5x5_dgrad"`` / ``"dwconv5x5_wgrad"``
+      ``"dwconv5x5s2_stats"`` / ``"dwconv5x5s2_dgrad"`` / ``"dwconv5x5s2_wgrad"``
+    The 5x5 ops' launches, tensors as for their 3x3 namesakes: path
+    ``"dwconv"`` with ``V``, ``lpr``, ``ctiles``, ``tile_h`` / ``tile_w`` (a
+    work item is a tile of that many pixels of one image), ``strip``,
+    ``items``, ``chunk_items``, ``nchunks``, ``trips`` (tiles a block visits;
+    for wgrad the strips of one tile a thread visits before its fp32 sums
+    move to fp64, so ``trips * strip <= flush_every``), ``flush_every``,
+    ``lds_bytes`` and, but for dgrad, ``finalize_trips``; or ``"ineligible"``.
     ``None`` entries of ``others`` are absent tensors.  The dual kinds
     report path ``"nhwc"`` with their single counterparts' numbers plus
     ``dual: True``, or ``"ineligible"`` where the dual kernels decline.
@@ -807,6 +850,8 @@ __all__ = [
     "conv1x1_stats",
     "dwconv3x3_stats",
     "dwconv3x3_backward",
+    "dwconv5x5_stats",
+    "dwconv5x5_backward",
     "batch_norm_stats_local_from_partials",
     "batch_norm_stats_packed_from_partials",
     "batch_norm_stats_local_grouped",

@@ -4559,6 +4559,35 @@ std::tuple<std::string, std::map<std::string, int64_t>> launch_plan(
     return {"dwconv", d};
   }
 
+  // depthwise 5x5 conv: others = {weight} (stats) or {weight, grad_y}
+  if (kind.rfind("dwconv5x5", 0) == 0) {
+    const bool stats = kind == "dwconv5x5_stats" || kind == "dwconv5x5s2_stats";
+    const bool dgrad = kind == "dwconv5x5_dgrad" || kind == "dwconv5x5s2_dgrad";
+    const bool wgrad = kind == "dwconv5x5_wgrad" || kind == "dwconv5x5s2_wgrad";
+    TORCH_CHECK(stats || dgrad || wgrad, "launch_plan: unknown kind ", kind);
+    if (!given(0) || (!stats && !given(1))) return {"ineligible", d};
+    const int64_t stride = kind.find("s2_") != std::string::npos ? 2 : 1;
+    const DwConv5x5Plan p =
+        stats   ? dwconv5x5_plan(input, *others[0], stride)
+        : wgrad ? dwconv5x5_wgrad_plan(input, *others[0], *others[1], stride)
+                : dwconv5x5_dgrad_plan(input, *others[0], *others[1], stride);
+    if (!p.ok) return {"ineligible", d};
+    d["V"] = p.v;
+    d["lpr"] = p.lpr;
+    d["ctiles"] = p.ctiles;
+    d["tile_h"] = p.tile_h;
+    d["tile_w"] = p.tile_w;
+    d["strip"] = p.strip;
+    d["items"] = p.items;
+    d["chunk_items"] = p.chunk_items;
+    d["nchunks"] = p.nchunks;
+    d["trips"] = p.trips;
+    d["flush_every"] = p.flush_every;
+    d["lds_bytes"] = (int64_t)p.lds_bytes;
+    if (!dgrad) d["finalize_trips"] = cdiv(p.nchunks, MSBN_WAVE);
+    return {"dwconv", d};
+  }
+
   // dual BN: the single counterparts' numbers plus "dual", or "ineligible"
   // where the ops decline and the composition runs
   if (kind == "elemt_dual" || kind == "bwd_elemt_dual") {

@@ -396,6 +396,56 @@ DwConvPlan dwconv3x3_wgrad_plan(const at::Tensor& input,
                                 const at::Tensor& weight,
                                 const at::Tensor& grad_y, int64_t stride);
 
+// ---- depthwise 5x5 conv + statistics, gradients (dwconv5x5_kernels.hip) ----
+// The 3x3 ops above at kernel 5x5, padding 2:
+//   y[n,c,oh,ow]  = sum_{kh,kw} x[n,c,oh*s-2+kh,ow*s-2+kw] * w[c,0,kh,kw]
+//   dx[n,c,ih,iw] = sum dy[n,c,oh,ow] * w[c,0,kh,kw] over the taps with
+//                   ih = oh*s-2+kh, iw = ow*s-2+kw inside dy
+//   dw[c,0,kh,kw] = sum over (n,oh,ow) dy[n,c,oh,ow] * x[n,c,oh*s-2+kh,
+//                   ow*s-2+kw] inside x
+// y: fp32, kh then kw ascending into one accumulator, rounded once; the
+// statistics are those of the rounded values.  dx: fp32, dy rows then dy
+// columns ascending, rounded once.  dw: at most MSBN_ACC_FLUSH fp32 terms
+// per accumulator, then fp64 (deterministic, no atomics), rounded once,
+// contiguous [C, 1, 5, 5].  Same returns and the same declines as the 3x3
+// ops, the weight being a contiguous [C, 1, 5, 5].
+std::tuple<at::Tensor, at::Tensor, int64_t> dwconv5x5_stats(
+    const at::Tensor& input, const at::Tensor& weight, int64_t stride);
+std::tuple<at::Tensor, at::Tensor> dwconv5x5_backward(
+    const at::Tensor& grad_y, const at::Tensor& input,
+    const at::Tensor& weight, int64_t stride, bool want_dx, bool want_dw);
+
+// The launches these ops would make (device not considered); ok == false
+// where they decline.  A work item is a tile of tile_h x tile_w pixels of one
+// image (of y for the forward and wgrad, of dx for dgrad); a thread row owns
+// strips of `strip` columns of it.  trips: tiles a block visits (forward,
+// dgrad), or strips of one tile a wgrad thread visits, whose fp32
+// accumulators move to fp64 after every tile: trips * strip <= flush_every.
+struct DwConv5x5Plan {
+  bool ok;
+  int64_t n, c, h, w, oh, ow;
+  int stride;
+  int v;                // channels of a lane
+  int lpr;              // lanes across the channel axis (8 or 16)
+  int ctiles;           // channel tiles
+  int tile_h, tile_w;   // pixels of a work item
+  int strip;            // columns of a thread row's strip
+  int64_t items;        // tiles
+  int64_t chunk_items;  // tiles of a chunk (block)
+  int nchunks;          // partials per channel (and tap)
+  int trips;
+  int flush_every;      // most fp32 terms between two flushes
+  size_t lds_bytes;     // static LDS of a block
+};
+DwConv5x5Plan dwconv5x5_plan(const at::Tensor& input, const at::Tensor& weight,
+                             int64_t stride);
+DwConv5x5Plan dwconv5x5_dgrad_plan(const at::Tensor& input,
+                                   const at::Tensor& weight,
+                                   const at::Tensor& grad_y, int64_t stride);
+DwConv5x5Plan dwconv5x5_wgrad_plan(const at::Tensor& input,
+                                   const at::Tensor& weight,
+                                   const at::Tensor& grad_y, int64_t stride);
+
 // batch_norm_stats_local / batch_norm_stats_packed with the partial stage
 // already done: they run bn_stats_finalize alone over `partials`
 // (fp64 [C][nchunks][2] of {sum x, sum x^2}, `count` elements per channel)
@@ -513,6 +563,13 @@ std::tuple<std::string, std::map<std::string, int64_t>> launch_plan_grouped(
 //                        input = x,      others = {weight, grad_y}: path
 //                        "dwconv" with the same numbers (finalize_trips for
 //                        wgrad alone), or "ineligible"
+//   "dwconv5x5_stats" / "dwconv5x5_dgrad" / "dwconv5x5_wgrad" (stride 1),
+//   "dwconv5x5s2_stats" / "dwconv5x5s2_dgrad" / "dwconv5x5s2_wgrad" (stride 2)
+//                        the same tensors as their 3x3 namesakes: path
+//                        "dwconv" with DwConv5x5Plan's numbers (V, lpr, ctiles,
+//                        tile_h, tile_w, strip, items, chunk_items, nchunks,
+//                        trips, flush_every, lds_bytes; finalize_trips for
+//                        stats and wgrad), or "ineligible"
 //   "stats_grouped" / "elemt_grouped"          input = x_0, others = {x_1 ..
 //                        x_{S-1}}; "bwd_reduce_grouped" / "bwd_elemt_grouped"
 //                        others = {x_1 .. x_{S-1}, dy_0 .. dy_{S-1}}: path

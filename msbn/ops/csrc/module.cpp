@@ -127,6 +127,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dwconv3x3_backward", &msbn::dwconv3x3_backward, py::arg("grad_y"),
         py::arg("input"), py::arg("weight"), py::arg("stride"),
         py::arg("want_dx"), py::arg("want_dw"));
+  m.def("dwconv5x5_stats", &msbn::dwconv5x5_stats, py::arg("input"),
+        py::arg("weight"), py::arg("stride") = 1);
+  m.def("dwconv5x5_backward", &msbn::dwconv5x5_backward, py::arg("grad_y"),
+        py::arg("input"), py::arg("weight"), py::arg("stride"),
+        py::arg("want_dx"), py::arg("want_dw"));
   m.def("batch_norm_stats_local_from_partials",
         &msbn::batch_norm_stats_local_from_partials, py::arg("partials"),
         py::arg("nchunks"), py::arg("count"), py::arg("eps"),
