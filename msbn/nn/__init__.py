@@ -17,6 +17,7 @@ from msbn.nn.frozen import (  # noqa: F401
     freeze_batchnorm,
 )
 from msbn.nn.fuse_pass import fuse_bn_act  # noqa: F401
+from msbn.nn.se import SqueezeExcite  # noqa: F401
 
 __all__ = [
     "FrozenBatchNorm2d",
@@ -31,4 +32,5 @@ __all__ = [
     "SyncBatchNormAct2d",
     "InPlaceSyncBatchNormActFunction",
     "fuse_bn_act",
+    "SqueezeExcite",
 ]

@@ -1025,9 +1025,186 @@ def dwconv3x3_with_stats(conv, bn, x: torch.Tensor,
     return conv(x), None
 
 
+class SyncBatchNormSiluSEFunction(torch.autograd.Function):
+    """``se(silu(bn(y)))`` for a training-mode BatchNorm and a squeeze-excite
+    block, as the stage ops ``ops.se_*`` (docs/KERNEL_DESIGN.md
+    "Squeeze-excite"): the activated tensor is never stored, the forward
+    reads ``y`` twice and writes once, the backward reads ``(grad, y)`` twice
+    and writes once, and the BatchNorm backward's per-channel sums come from
+    per-image tables instead of a pass of their own.
+
+    Statistics and collectives are ``SyncBatchNormActFunction``'s:
+    ``compute_sync_stats`` (from ``partials`` where given) forward, one
+    ``[2C]`` all_reduce backward.  Saved for backward: ``y``, the BatchNorm's
+    per-channel tensors, the per-image tables ``g``, ``s``, ``hpre``, ``Q``
+    and the SE parameters.  Callers check ``bn_silu_se_eligible`` for GPU
+    tensors; CPU tensors run the reference ops."""
+
+    @staticmethod
+    def forward(ctx, y, weight, bias, running_mean, running_var, eps: float,
+                momentum: float, process_group, world_size: int, w1, b1, w2,
+                b2, partials=None, nchunks=None):
+        y = _contig(y)
+        if weight is not None:
+            weight = weight.contiguous()
+        if bias is not None:
+            bias = bias.contiguous()
+        mean, invstd, count_sum, coefs = compute_sync_stats(
+            y, eps, momentum, running_mean, running_var, process_group,
+            world_size, weight, bias, want_coefs=True, partials=partials,
+            nchunks=nchunks,
+        )
+        if coefs is None:  # the CPU statistics come without them
+            from msbn.ops._reference import _act_coefs
+            coefs = torch.cat(_act_coefs(mean, invstd, weight, bias))
+        ctx.use_sync = world_size > 1 or (
+            process_group is not None and _force_sync()
+        )
+        ctx.process_group = process_group
+        ctx.has_weight = weight is not None
+        ctx.has_bias = bias is not None
+        ctx.bias_dtype = bias.dtype if bias is not None else None
+        hw = y.shape[2] * y.shape[3]
+        parts = ops.se_squeeze(y, coefs, mean)
+        if parts is None:
+            raise RuntimeError("se_squeeze declined tensors its plan takes")
+        s, hpre, g, q = ops.se_gate(parts, hw, w1, b1, w2, b2)
+        if g is None:
+            raise RuntimeError("se_gate declined parameters its plan takes")
+        out = ops.se_scale(y, coefs, g)
+        saved = (y, mean, invstd, count_sum, coefs, g, s, hpre, q, w1, w2)
+        if ctx.has_weight:
+            saved += (weight,)
+        ctx.save_for_backward(*saved)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        saved = ctx.saved_tensors
+        y, mean, invstd, count_sum, coefs, g, s, hpre, q, w1, w2 = saved[:11]
+        weight = saved[11] if ctx.has_weight else None
+        need = ctx.needs_input_grad
+        grad_output = _match_layout(grad_output, y)
+        C = int(y.shape[1])
+        hw = y.shape[2] * y.shape[3]
+        parts = ops.se_backward_reduce(grad_output, y, coefs, mean)
+        if parts is None:
+            raise RuntimeError(
+                "se_backward_reduce declined a gradient laid out like y")
+        dpool, dz2, dz1, p = ops.se_gate_backward(parts, hw, g, hpre, w1, w2)
+        if dpool is None:
+            raise RuntimeError("se_gate_backward declined the saved tables")
+        need_weight_g = ctx.has_weight and need[1]
+        need_bias_g = ctx.has_bias and need[2]
+        sum_dy, sum_dy_xmu, grad_weight, grad_bias = ops.se_backward_finalize(
+            g, dpool, p, q, invstd, need_weight_g, need_bias_g)
+        if sum_dy is None:
+            raise RuntimeError("se_backward_finalize declined the tables")
+        dw1, db1, dw2, db2 = se_grads = ops.se_param_backward(
+            dz2, dz1, hpre, s, w1, w2, need[9], need[10], need[11], need[12])
+        if any(need[9:13]) and all(t is None for t in se_grads):
+            raise RuntimeError("se_param_backward declined the tables")
+        grad_input = None
+        if need[0]:
+            if ctx.use_sync:
+                combined, copied = _combined_view(sum_dy, sum_dy_xmu, C)
+                from msbn.utils import debug as _dbg
+                if _dbg.enabled():
+                    _dbg.verify_collective("syncbn.bwd.all_reduce",
+                                           combined, ctx.process_group)
+                dist.all_reduce(combined, dist.ReduceOp.SUM,
+                                group=ctx.process_group)
+                from msbn.utils.logging import comm_log
+                comm_log.record("all_reduce", combined.numel() * 4,
+                                f"syncbn bwd C={C}")
+                if copied:
+                    sum_dy, sum_dy_xmu = combined[:C], combined[C:]
+            grad_input = ops.se_backward_elemt(
+                grad_output, y, coefs, g, dpool, mean, invstd,
+                None if weight is None else weight.float(), sum_dy,
+                sum_dy_xmu, count_sum)
+        # the [C] affine gradients leave the kernel in fp32
+        if grad_weight is not None:
+            grad_weight = grad_weight.to(weight.dtype)
+        if grad_bias is not None:
+            grad_bias = grad_bias.to(ctx.bias_dtype)
+        return (grad_input, grad_weight, grad_bias, None, None, None, None,
+                None, None, dw1, db1, dw2, db2, None, None)
+
+
+def bn_silu_se_eligible(bn, se, y: torch.Tensor) -> bool:
+    """True when ``se(bn(y))`` runs as ``SyncBatchNormSiluSEFunction``: ``bn``
+    exactly a ``SyncBatchNormAct2d`` with ``act="silu"`` that
+    ``_takes_partials`` (training, out of place, no hooks), ``se`` exactly a
+    ``SqueezeExcite`` without hooks whose four parameters share a dtype and
+    sit on ``y``'s device, autocast off, and ``y`` a non-empty CUDA bf16 /
+    half dense channels-last tensor with ``C`` a multiple of 8 at a 16-byte
+    aligned address, ``C`` and ``Cr`` within the gate kernels' tables
+    (``ops.launch_plan("se_gate", ...)``)."""
+    from msbn.nn.se import SqueezeExcite
+    if not (
+        type(bn) is SyncBatchNormAct2d and getattr(bn, "act", None) == "silu"
+        and _takes_partials(bn)
+        and type(se) is SqueezeExcite
+        and not (_hooked(se) or _hooked(se.fc1) or _hooked(se.fc2))
+        and type(se.fc1) is torch.nn.Conv2d and type(se.fc2) is torch.nn.Conv2d
+        and se.fc1.bias is not None and se.fc2.bias is not None
+        and not torch.is_autocast_enabled()
+        and y.is_cuda and y.dim() == 4 and y.numel() > 0
+    ):
+        return False
+    params = (se.fc1.weight, se.fc1.bias, se.fc2.weight, se.fc2.bias)
+    if not all(t.device == y.device and t.is_contiguous()
+               and t.dtype == params[0].dtype for t in params):
+        return False
+    plan = ops.launch_plan("se_gate", y, (se.fc1.weight, se.fc2.weight))
+    return plan["path"] == "se_gate"
+
+
+def bn_silu_se(bn, se, y: torch.Tensor, partials=None):
+    """``se(bn(y))`` for a BatchNorm+SiLU layer and the squeeze-excite block
+    after it.  Where ``bn_silu_se_eligible`` the pair runs as
+    ``SyncBatchNormSiluSEFunction``: 3 passes over the activation forward and
+    5 backward, what the BatchNorm+SiLU layer alone costs, and the activated
+    tensor is not kept.  ``partials``: ``y`` came out of a convolution kernel
+    together with the BatchNorm's partial statistics (``conv1x1_with_stats``
+    and its depthwise siblings).  Anything else is exactly the composition:
+    eval mode, fp32, NCHW, CPU, an empty rank, hooks, autocast."""
+    if not bn_silu_se_eligible(bn, se, y):
+        return se(_bn_call(bn, y, None, False, partials))
+    bn._check_input_dim(y)
+    bn._check_non_zero_input_channels(y)
+    if bn.track_running_stats and bn.num_batches_tracked is not None:
+        bn.num_batches_tracked.add_(1)
+    process_group = None
+    world_size = 1
+    if dist.is_available() and dist.is_initialized():
+        process_group = bn.process_group or dist.group.WORLD
+        world_size = dist.get_world_size(process_group)
+    running_mean = bn.running_mean if bn.track_running_stats else None
+    running_var = bn.running_var if bn.track_running_stats else None
+    return SyncBatchNormSiluSEFunction.apply(
+        y, bn.weight, bn.bias, running_mean, running_var, bn.eps,
+        _momentum_factor(bn), process_group, world_size, se.fc1.weight,
+        se.fc1.bias, se.fc2.weight, se.fc2.bias, partials,
+        None if partials is None else int(partials.shape[1]),
+    )
+
+
+def _dw_bn_tail(bn, se, y, residual, fork, partials):
+    """What follows the depthwise convolution: the BatchNorm, or with ``se``
+    the BatchNorm and the squeeze-excite block after it."""
+    if se is None:
+        return _bn_call(bn, y, residual, fork, partials)
+    if residual is not None or fork:
+        raise ValueError("se= takes neither a residual nor fork=True")
+    return bn_silu_se(bn, se, y, partials)
+
+
 def dwconv3x3_bn_act(conv, bn, x: torch.Tensor,
                      residual: Optional[torch.Tensor] = None,
-                     fork: bool = False, *, grad_kernels: bool = False):
+                     fork: bool = False, *, grad_kernels: bool = False,
+                     se=None):
     """``bn(conv(x), residual=residual, fork=fork)`` for a depthwise 3x3
     convolution and the BatchNorm after it.  Where ``dwconv_stats_eligible``
     the convolution runs as this project's streaming kernel, which forms the
@@ -1039,24 +1216,29 @@ def dwconv3x3_bn_act(conv, bn, x: torch.Tensor,
     ``grad_kernels=True`` also runs that convolution's backward through
     ``ops.dwconv3x3_backward`` (both gradients as this project's kernels;
     the stock backward for whatever they decline).  It has no effect where
-    the composition runs."""
+    the composition runs.
+
+    ``se``: a ``SqueezeExcite`` applied to the layer's output; the call then
+    returns ``bn_silu_se(bn, se, conv(x), partials)`` and takes neither
+    ``residual`` nor ``fork``."""
     y, partials = dwconv3x3_with_stats(conv, bn, x, grad_kernels)
-    return _bn_call(bn, y, residual, fork, partials)
+    return _dw_bn_tail(bn, se, y, residual, fork, partials)
 
 
 def dwconv5x5_bn_act(conv, bn, x: torch.Tensor,
                      residual: Optional[torch.Tensor] = None,
-                     fork: bool = False, *, grad_kernels: bool = False):
+                     fork: bool = False, *, grad_kernels: bool = False,
+                     se=None):
     """``dwconv3x3_bn_act`` for a depthwise 5x5 convolution (padding 2):
     ``ops.dwconv5x5_stats`` where ``dwconv5x5_stats_eligible``, with
     ``grad_kernels=True`` its backward through ``ops.dwconv5x5_backward``;
-    exactly the composition otherwise."""
+    exactly the composition otherwise.  ``se`` as there."""
     if dwconv5x5_stats_eligible(conv, bn, x):
         y, partials = DwConv5x5StatsFunction.apply(
             x, conv.weight, _pair(conv.stride)[0], grad_kernels)
     else:
         y, partials = conv(x), None
-    return _bn_call(bn, y, residual, fork, partials)
+    return _dw_bn_tail(bn, se, y, residual, fork, partials)
 
 
 def bn_add_bn_act(bn, bn_skip, x: torch.Tensor, x_skip: torch.Tensor,

@@ -643,6 +643,123 @@ def dwconv5x5_backward(grad_y: torch.Tensor, input: torch.Tensor,
     return dx, dw
 
 
+def se_squeeze(y: torch.Tensor, coefs: torch.Tensor, mean: torch.Tensor):
+    """First forward stage of squeeze-excite after BN+SiLU
+    (docs/KERNEL_DESIGN.md "Squeeze-excite").  With ``z = scale*y + shift``
+    (``coefs = [scale | shift]``, fp32) and ``a = silu(z)``, one read of ``y``
+    gives per image and channel ``S = sum a``, ``Q1 = sum silu'(z)`` and
+    ``Q2 = sum silu'(z)*(y - mean)``: fp64 partials ``[N, chunks, C, 3]``,
+    which ``se_gate`` finalizes.
+
+    Returns ``None`` and launches nothing for a GPU tensor the streaming
+    kernels do not take: anything but a non-empty dense channels-last 4-D
+    bf16 / half tensor with ``C`` a multiple of 8 at a 16-byte aligned
+    address.  CPU tensors run the plain-PyTorch reference."""
+    if y.is_cuda:
+        return _require_hip().se_squeeze(y, coefs, mean, None)
+    return _ref.se_squeeze(y, coefs, mean)
+
+
+def se_gate(partials: torch.Tensor, hw: int, w1, b1, w2, b2):
+    """The excite MLP, one block per image: ``(s, hpre, g, Q)`` with
+    ``s[N, C] = S / hw``, ``hpre[N, Cr] = W1 s + b1``, ``g[N, C] =
+    sigmoid(W2 silu(hpre) + b2)`` and ``Q[N, C, 2] = {Q1, Q2}`` (sums), all
+    fp32.  ``w1`` is ``[Cr, C]`` or ``[Cr, C, 1, 1]``, ``w2`` ``[C, Cr(, 1,
+    1)]``; the four parameters share one dtype (fp32, bf16 or half) and all
+    arithmetic is fp32.
+
+    Returns ``(None, None, None, None)`` and launches nothing for GPU tensors
+    the kernel does not take: anything but ``se_squeeze``'s fp64 partials and
+    contiguous parameters of one dtype on one device with ``C <= 4096`` and
+    ``1 <= Cr <= 1024``."""
+    if partials.is_cuda:
+        return _require_hip().se_gate(partials, int(hw), w1, b1, w2, b2)
+    return _ref.se_gate(partials, int(hw), w1, b1, w2, b2)
+
+
+def se_scale(y: torch.Tensor, coefs: torch.Tensor, g: torch.Tensor):
+    """``out = silu(scale*y + shift) * g[n, c]``, rounded to ``y``'s dtype
+    once.  ``None`` where ``se_squeeze`` declines."""
+    if y.is_cuda:
+        return _require_hip().se_scale(y, coefs, g)
+    return _ref.se_scale(y, coefs, g)
+
+
+def se_backward_reduce(grad_out, y, coefs, mean):
+    """First backward stage: one read of ``(grad_out, y)`` gives per image
+    and channel ``R = sum dout*a``, ``P1 = sum dout*silu'(z)`` and ``P2 = sum
+    dout*silu'(z)*(y - mean)``, as partials laid out like ``se_squeeze``'s.
+    ``None`` where ``se_squeeze`` declines or ``grad_out`` is not a dense
+    channels-last twin of ``y`` at a 16-byte aligned address."""
+    if y.is_cuda:
+        return _require_hip().se_squeeze(y, coefs, mean, grad_out)
+    return _ref.se_squeeze(y, coefs, mean, grad_out)
+
+
+def se_gate_backward(partials, hw: int, g, hpre, w1, w2):
+    """The excite MLP's backward, one block per image: ``(dpool, dz2, dz1,
+    P)`` with ``dz2[N, C] = R*g*(1 - g)``, ``dz1[N, Cr] = (W2^T dz2) *
+    silu'(hpre)``, ``dpool[N, C] = (W1^T dz1) / hw`` (the gradient reaching
+    every pixel of ``a`` through the pool) and ``P[N, C, 2] = {P1, P2}``.
+    Four ``None`` with nothing launched where ``se_gate`` declines or ``g`` /
+    ``hpre`` are not its fp32 outputs."""
+    if partials.is_cuda:
+        return _require_hip().se_gate_backward(partials, int(hw), g, hpre,
+                                               w1, w2)
+    return _ref.se_gate_backward(partials, int(hw), g, hpre, w1, w2)
+
+
+def se_backward_finalize(g, dpool, p, q, invstd, weight_g: bool,
+                         bias_g: bool):
+    """The BatchNorm backward's per-channel sums without a second pass over
+    the activation: the gradient entering BN+SiLU is ``(dout*g + dpool) *
+    silu'(z)``, so ``sum_dy = sum_n g*P1 + dpool*Q1`` and ``sum_dy_xmu =
+    sum_n g*P2 + dpool*Q2`` (fp64, fixed order).  Returns ``(sum_dy,
+    sum_dy_xmu, grad_weight, grad_bias)``; on the GPU the two sums are views
+    of one ``[2C]`` buffer (one all_reduce).  Four ``None`` with nothing
+    launched for GPU tensors that are not the contiguous fp32 tables of one
+    device."""
+    if g.is_cuda:
+        sum_dy, sum_dy_xmu, gw, gb = _require_hip().se_bn_finalize_backward(
+            g, dpool, p, q, invstd, bool(weight_g), bool(bias_g))
+        return (sum_dy, sum_dy_xmu, gw if weight_g else None,
+                gb if bias_g else None)
+    return _ref.se_backward_finalize(g, dpool, p, q, invstd, weight_g, bias_g)
+
+
+def se_param_backward(dz2, dz1, hpre, s, w1, w2, want_w1: bool = True,
+                      want_b1: bool = True, want_w2: bool = True,
+                      want_b2: bool = True):
+    """The SE block's own gradients ``(dW1, db1, dW2, db2)``, shaped and typed
+    like the parameters, ``None`` where not wanted: ``dW2 = dz2^T silu(hpre)``,
+    ``db2 = sum_n dz2``, ``dW1 = dz1^T s``, ``db1 = sum_n dz1``; fp64 over
+    ``n`` ascending, rounded once.  Four ``None`` with nothing launched for
+    GPU tensors the kernel does not take (``se_gate``'s rules for the
+    weights, contiguous fp32 tables)."""
+    wants = (bool(want_w1), bool(want_b1), bool(want_w2), bool(want_b2))
+    if dz2.is_cuda:
+        out = _require_hip().se_param_backward(dz2, dz1, hpre, s, w1, w2,
+                                               *wants)
+        return tuple(t if w else None for t, w in zip(out, wants))
+    return _ref.se_param_backward(dz2, dz1, hpre, s, w1, w2, *wants)
+
+
+def se_backward_elemt(grad_out, y, coefs, g, dpool, mean, invstd, weight,
+                      sum_dy, sum_dy_xmu, count):
+    """Last backward stage: ``dy = a*gz + b*y + d`` with ``gz = (grad_out*g +
+    dpool) * silu'(z)`` recomputed per element and the coefficients of
+    ``batch_norm_backward_elemt`` from ``sum_dy`` / ``sum_dy_xmu`` (summed
+    over the ranks) and ``count``; rounded once.  ``weight`` is the
+    BatchNorm's, fp32 or None.  ``None`` where ``se_backward_reduce``
+    declines."""
+    if y.is_cuda:
+        return _require_hip().se_backward_elemt(
+            grad_out, y, coefs, g, dpool, mean, invstd, weight, sum_dy,
+            sum_dy_xmu, count)
+    return _ref.se_backward_elemt(grad_out, y, coefs, g, dpool, mean, invstd,
+                                  weight, sum_dy, sum_dy_xmu, count)
+
+
 def batch_norm_stats_local_from_partials(partials, nchunks: int, count: int,
                                          eps: float, running_mean,
                                          running_var, momentum: float,
@@ -801,6 +918,16 @@ def launch_plan(kind: str, input: torch.Tensor, others=(), coefs=None) -> dict:
     for wgrad the strips of one tile a thread visits before its fp32 sums
     move to fp64, so ``trips * strip <= flush_every``), ``flush_every``,
     ``lds_bytes`` and, but for dgrad, ``finalize_trips``; or ``"ineligible"``.
+      ``"se_squeeze"`` / ``"se_scale"``        input = y
+      ``"se_bwd_reduce"`` / ``"se_bwd_elemt"``  input = y, others = (grad_out,)
+      ``"se_gate"`` / ``"se_gate_bwd"``         input = y, others = (w1, w2)
+    The squeeze-excite ops' launches: path ``"se"`` (``"se_gate"`` for the
+    gate kinds, which add ``Cr`` and ``lds_bytes``) with ``V``, ``lpr``,
+    ``ctiles``, ``chunk_rows``, ``chunks_per_image`` (blocks per image and
+    channel tile), ``trips``, ``flush_every`` and ``finalize_trips`` (the
+    trips of the per-channel sum over the images), or ``"ineligible"``
+    where the ops decline; empty and fp32 tensors are declined, not raised
+    for.
     ``None`` entries of ``others`` are absent tensors.  The dual kinds
     report path ``"nhwc"`` with their single counterparts' numbers plus
     ``dual: True``, or ``"ineligible"`` where the dual kernels decline.
@@ -852,6 +979,14 @@ __all__ = [
     "dwconv3x3_backward",
     "dwconv5x5_stats",
     "dwconv5x5_backward",
+    "se_squeeze",
+    "se_gate",
+    "se_scale",
+    "se_backward_reduce",
+    "se_gate_backward",
+    "se_backward_finalize",
+    "se_param_backward",
+    "se_backward_elemt",
     "batch_norm_stats_local_from_partials",
     "batch_norm_stats_packed_from_partials",
     "batch_norm_stats_local_grouped",

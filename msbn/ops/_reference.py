@@ -539,3 +539,107 @@ def batch_norm_backward_elemt(
         - (x - _chan_view(mean.to(torch.float32), input)) * _chan_view(proj, input)
     ) * _chan_view(f_scale, input)
     return dx.to(grad_out.dtype)
+
+
+# ---- squeeze-excite after BN+SiLU ------------------------------------------
+# The stage ops of docs/KERNEL_DESIGN.md "Squeeze-excite" in plain PyTorch, at
+# the wider of fp32 and the tensors' own dtype (so fp64 tensors stay fp64:
+# tests pin the factorised BN sums with them).  Partials are [N, 1, C, 3].
+
+def _se_float(t: torch.Tensor) -> torch.dtype:
+    return torch.promote_types(t.dtype, torch.float32)
+
+
+def _se_z(y, coefs):
+    ft = _se_float(y)
+    C = y.shape[1]
+    yf = y.to(ft)
+    z = yf * coefs[:C].to(ft).view(1, C, 1, 1) + coefs[C:].to(ft).view(
+        1, C, 1, 1)
+    return yf, z
+
+
+def _silu_grad(z):
+    sg = torch.sigmoid(z)
+    return sg * (1.0 + z * (1.0 - sg))
+
+
+def se_squeeze(y, coefs, mean, grad_out=None):
+    """{S, Q1, Q2} per image and channel, or {R, P1, P2} with ``grad_out``."""
+    yf, z = _se_z(y, coefs)
+    a, d1 = z * torch.sigmoid(z), _silu_grad(z)
+    if grad_out is not None:
+        d = grad_out.to(yf.dtype)
+        a, d1 = a * d, d1 * d
+    xmu = yf - mean.to(yf.dtype).view(1, -1, 1, 1)
+    parts = torch.stack(
+        [a.sum((2, 3)), d1.sum((2, 3)), (d1 * xmu).sum((2, 3))], dim=-1)
+    return parts.to(torch.float64).unsqueeze(1).contiguous()
+
+
+def se_gate(partials, hw: int, w1, b1, w2, b2):
+    ft = _se_float(w1)
+    tot = partials.sum(1)
+    Cr, C = w1.shape[0], w2.shape[0]
+    s = (tot[..., 0] / hw).to(ft)
+    hpre = s @ w1.reshape(Cr, C).to(ft).t() + b1.to(ft)
+    h = hpre * torch.sigmoid(hpre)
+    g = torch.sigmoid(h @ w2.reshape(C, Cr).to(ft).t() + b2.to(ft))
+    return s, hpre, g, tot[..., 1:].to(ft).contiguous()
+
+
+def se_scale(y, coefs, g):
+    _, z = _se_z(y, coefs)
+    N, C = y.shape[:2]
+    return (z * torch.sigmoid(z) * g.to(z.dtype).view(N, C, 1, 1)).to(y.dtype)
+
+
+def se_gate_backward(partials, hw: int, g, hpre, w1, w2):
+    ft = g.dtype
+    tot = partials.sum(1)
+    Cr, C = w1.shape[0], w2.shape[0]
+    dz2 = tot[..., 0].to(ft) * g * (1.0 - g)
+    dh = dz2 @ w2.reshape(C, Cr).to(ft)
+    dz1 = dh * _silu_grad(hpre)
+    dpool = dz1 @ w1.reshape(Cr, C).to(ft) / hw
+    return dpool, dz2, dz1, tot[..., 1:].to(ft).contiguous()
+
+
+def se_backward_finalize(g, dpool, p, q, invstd, weight_g: bool,
+                         bias_g: bool):
+    ft = g.dtype
+    g64, dp64 = g.double(), dpool.double()
+    s_dy = (g64 * p[..., 0].double() + dp64 * q[..., 0].double()).sum(0)
+    s_dy_xmu = (g64 * p[..., 1].double() + dp64 * q[..., 1].double()).sum(0)
+    gw = (s_dy_xmu * invstd.double()).to(ft) if weight_g else None
+    gb = s_dy.to(ft) if bias_g else None
+    return s_dy.to(ft), s_dy_xmu.to(ft), gw, gb
+
+
+def se_param_backward(dz2, dz1, hpre, s, w1, w2, want_w1: bool, want_b1: bool,
+                      want_w2: bool, want_b2: bool):
+    h = (hpre * torch.sigmoid(hpre)).double()
+    dw1 = (dz1.double().t() @ s.double()).reshape(w1.shape).to(w1.dtype)
+    dw2 = (dz2.double().t() @ h).reshape(w2.shape).to(w2.dtype)
+    return (dw1 if want_w1 else None,
+            dz1.double().sum(0).to(w1.dtype) if want_b1 else None,
+            dw2 if want_w2 else None,
+            dz2.double().sum(0).to(w1.dtype) if want_b2 else None)
+
+
+def se_backward_elemt(grad_out, y, coefs, g, dpool, mean, invstd, weight,
+                      sum_dy, sum_dy_xmu, count):
+    yf, z = _se_z(y, coefs)
+    ft = yf.dtype
+    N, C = y.shape[:2]
+    gz = (grad_out.to(ft) * g.to(ft).view(N, C, 1, 1)
+          + dpool.to(ft).view(N, C, 1, 1)) * _silu_grad(z)
+    n = count.sum().to(ft)
+    istd = invstd.to(ft)
+    f1 = istd * (weight.to(ft) if weight is not None else 1.0)
+    f2 = sum_dy.to(ft) / n
+    f3 = istd * istd * sum_dy_xmu.to(ft) / n
+    dy = (gz - f2.view(1, C, 1, 1)
+          - (yf - mean.to(ft).view(1, C, 1, 1)) * f3.view(1, C, 1, 1)
+          ) * f1.view(1, C, 1, 1)
+    return dy.to(y.dtype)

@@ -4480,6 +4480,8 @@ std::tuple<std::string, std::map<std::string, int64_t>> launch_plan(
   if (kind == "stats_grouped" || kind == "elemt_grouped" ||
       kind == "bwd_reduce_grouped" || kind == "bwd_elemt_grouped")
     return launch_plan_grouped(kind, input, others);
+  // squeeze-excite: declines where the other kinds raise (empty, fp32)
+  if (kind.rfind("se_", 0) == 0) return launch_plan_se(kind, input, others);
   TORCH_CHECK(input.dim() >= 2 && input.numel() > 0,
               "launch_plan: input must be a non-empty >= 2-D tensor");
   const int esize = (int)input.element_size();

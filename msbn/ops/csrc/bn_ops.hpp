@@ -529,6 +529,102 @@ std::tuple<std::string, std::map<std::string, int64_t>> launch_plan_grouped(
     const std::string& kind, const at::Tensor& input,
     const std::vector<c10::optional<at::Tensor>>& others);
 
+// ---- squeeze-excite after BN+SiLU (se_kernels.hip) -------------------------
+// For y a dense channels-last bf16 / half [N, C, H, W] (the depthwise conv
+// output), coefs = [scale(C) | shift(C)] fp32 of the training BatchNorm:
+//   z = scale*y + shift, a = silu(z) (fp32, never stored)
+//   s[n,c] = mean_hw a, h = silu(W1 s + b1), g = sigmoid(W2 h + b2)
+//   out = a * g[n,c], rounded once
+// docs/KERNEL_DESIGN.md "Squeeze-excite".  Every fp32 table below is
+// contiguous; reductions are deterministic (no atomics).
+//
+// The streaming ops decline -- an undefined tensor, nothing launched -- for
+// whatever se_plan declines (and a grad_out that is not y's twin); the small
+// ops (gate, gate backward, BN finalize, parameter gradients) decline with a
+// tuple of four undefined tensors for anything but what their comments name.
+
+// How the streaming kernels tile y; ok == false where they decline: anything
+// but a non-empty dense channels-last 4-D bf16 / half tensor with C a
+// multiple of 8 at a 16-byte aligned address and N <= 65535.
+struct SePlan {
+  bool ok;
+  int64_t n, c, hw;
+  int v;                 // channels of a lane
+  int lpr;               // lanes across the channel axis
+  int ctiles;            // channel tiles
+  int chunk_rows;        // pixels of a chunk (a multiple of 256 / lpr)
+  int chunks_per_image;  // blocks (and partials) per image and channel tile
+  int trips;             // pixels one thread visits
+  int flush_every;       // most fp32 terms between two flushes
+};
+SePlan se_plan(const at::Tensor& y);
+
+// C and Cr within the gate kernels' LDS tables
+bool se_gate_fits(int64_t C, int64_t Cr);
+
+// Partials fp64 [N, chunks, C, 3].  Without grad_out: {S = sum a, Q1 = sum
+// silu'(z), Q2 = sum silu'(z)(y - mean)} per image and channel; with
+// grad_out (y's twin): {R = sum dout a, P1 = sum dout silu'(z), P2 = sum dout
+// silu'(z)(y - mean)}.
+at::Tensor se_squeeze(const at::Tensor& y, const at::Tensor& coefs,
+                      const at::Tensor& mean,
+                      const c10::optional<at::Tensor>& grad_out);
+
+// (s[N,C], hpre[N,Cr], g[N,C], Q[N,C,2]) from the forward partials of images
+// of hw pixels.  w1 [Cr, C(, 1, 1)], b1 [Cr], w2 [C, Cr(, 1, 1)], b2 [C]:
+// contiguous, one dtype (fp32 / bf16 / half); C <= 4096, 1 <= Cr <= 1024.
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> se_gate(
+    const at::Tensor& partials, int64_t hw, const at::Tensor& w1,
+    const at::Tensor& b1, const at::Tensor& w2, const at::Tensor& b2);
+
+at::Tensor se_scale(const at::Tensor& y, const at::Tensor& coefs,
+                    const at::Tensor& g);
+
+// (dpool[N,C], dz2[N,C], dz1[N,Cr], P[N,C,2]) from the backward partials:
+// dz2 = R g (1 - g), dz1 = (W2^T dz2) silu'(hpre), dpool = W1^T dz1 / hw.
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> se_gate_backward(
+    const at::Tensor& partials, int64_t hw, const at::Tensor& g,
+    const at::Tensor& hpre, const at::Tensor& w1, const at::Tensor& w2);
+
+// (sum_dy, sum_dy_xmu, grad_weight, grad_bias) of the BatchNorm, the two sums
+// views of one fp32 [2C] buffer:
+//   sum_dy = sum_n g*P1 + dpool*Q1, sum_dy_xmu = sum_n g*P2 + dpool*Q2 (fp64)
+//   grad_weight = sum_dy_xmu * invstd, grad_bias = sum_dy (fp32, or undefined)
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor>
+se_bn_finalize_backward(const at::Tensor& g, const at::Tensor& dpool,
+                        const at::Tensor& p, const at::Tensor& q,
+                        const at::Tensor& invstd, bool weight_g, bool bias_g);
+
+// (dW1, db1, dW2, db2) of the SE block in the weights' dtype, each undefined
+// where not wanted: dW2 = dz2^T silu(hpre), db2 = sum_n dz2, dW1 = dz1^T s,
+// db1 = sum_n dz1; fp64 over n ascending, rounded once.
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> se_param_backward(
+    const at::Tensor& dz2, const at::Tensor& dz1, const at::Tensor& hpre,
+    const at::Tensor& s, const at::Tensor& w1, const at::Tensor& w2,
+    bool want_w1, bool want_b1, bool want_w2, bool want_b2);
+
+// dy = A*gz + B*y + D with gz = (grad_out*g + dpool) * silu'(z) and the
+// coefficients of batch_norm_backward_elemt (fp32 weight or none); sum_dy /
+// sum_dy_xmu are the sums over all ranks, count a 1-element fp32 tensor.
+at::Tensor se_backward_elemt(const at::Tensor& grad_out, const at::Tensor& y,
+                             const at::Tensor& coefs, const at::Tensor& g,
+                             const at::Tensor& dpool, const at::Tensor& mean,
+                             const at::Tensor& invstd,
+                             const c10::optional<at::Tensor>& weight,
+                             const at::Tensor& sum_dy,
+                             const at::Tensor& sum_dy_xmu,
+                             const at::Tensor& count);
+
+// launch_plan for the kinds "se_squeeze", "se_scale" (input = y),
+// "se_bwd_reduce", "se_bwd_elemt" (others = {grad_out}): path "se"; and
+// "se_gate", "se_gate_bwd" (input = y, others = {w1, w2}): path "se_gate"
+// with Cr and lds_bytes.  All report V, lpr, ctiles, chunk_rows,
+// chunks_per_image, trips, flush_every and finalize_trips (the trips of the
+// per-channel sum over the images), or "ineligible".
+std::tuple<std::string, std::map<std::string, int64_t>> launch_plan_se(
+    const std::string& kind, const at::Tensor& input,
+    const std::vector<c10::optional<at::Tensor>>& others);
+
 // ---- launch plan (host only, launches nothing) ----------------------------
 // Which kernel path a call would take and how far its loops run, decided by
 // the same host code the ops launch with.  kind / tensors:
@@ -574,6 +670,8 @@ std::tuple<std::string, std::map<std::string, int64_t>> launch_plan_grouped(
 //                        x_{S-1}}; "bwd_reduce_grouped" / "bwd_elemt_grouped"
 //                        others = {x_1 .. x_{S-1}, dy_0 .. dy_{S-1}}: path
 //                        "nhwc" or "ineligible" (launch_plan_grouped)
+//   "se_squeeze" / "se_scale" / "se_bwd_reduce" / "se_bwd_elemt" / "se_gate" /
+//   "se_gate_bwd"        launch_plan_se
 // (pass only what the op itself would dereference).  Returns (path, numbers):
 // path is "nchw_vec" | "nchw_flat" | "nhwc" | "small_plane" | "ineligible";
 // the dual kinds report "nhwc" with their single counterparts' numbers plus

@@ -132,6 +132,26 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dwconv5x5_backward", &msbn::dwconv5x5_backward, py::arg("grad_y"),
         py::arg("input"), py::arg("weight"), py::arg("stride"),
         py::arg("want_dx"), py::arg("want_dw"));
+  m.def("se_squeeze", &msbn::se_squeeze, py::arg("y"), py::arg("coefs"),
+        py::arg("mean"), py::arg("grad_out") = py::none());
+  m.def("se_gate", &msbn::se_gate, py::arg("partials"), py::arg("hw"),
+        py::arg("w1"), py::arg("b1"), py::arg("w2"), py::arg("b2"));
+  m.def("se_scale", &msbn::se_scale, py::arg("y"), py::arg("coefs"),
+        py::arg("g"));
+  m.def("se_gate_backward", &msbn::se_gate_backward, py::arg("partials"),
+        py::arg("hw"), py::arg("g"), py::arg("hpre"), py::arg("w1"),
+        py::arg("w2"));
+  m.def("se_bn_finalize_backward", &msbn::se_bn_finalize_backward,
+        py::arg("g"), py::arg("dpool"), py::arg("p"), py::arg("q"),
+        py::arg("invstd"), py::arg("weight_g"), py::arg("bias_g"));
+  m.def("se_param_backward", &msbn::se_param_backward, py::arg("dz2"),
+        py::arg("dz1"), py::arg("hpre"), py::arg("s"), py::arg("w1"),
+        py::arg("w2"), py::arg("want_w1"), py::arg("want_b1"),
+        py::arg("want_w2"), py::arg("want_b2"));
+  m.def("se_backward_elemt", &msbn::se_backward_elemt, py::arg("grad_out"),
+        py::arg("y"), py::arg("coefs"), py::arg("g"), py::arg("dpool"),
+        py::arg("mean"), py::arg("invstd"), py::arg("weight"),
+        py::arg("sum_dy"), py::arg("sum_dy_xmu"), py::arg("count"));
   m.def("batch_norm_stats_local_from_partials",
         &msbn::batch_norm_stats_local_from_partials, py::arg("partials"),
         py::arg("nchunks"), py::arg("count"), py::arg("eps"),

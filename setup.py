@@ -26,6 +26,7 @@ ext = CUDAExtension(
         os.path.join(CSRC, "dwconv_grad_kernels.hip"),
         os.path.join(CSRC, "dwconv5x5_kernels.hip"),
         os.path.join(CSRC, "grouped_bn_kernels.hip"),
+        os.path.join(CSRC, "se_kernels.hip"),
     ],
     include_dirs=[CSRC],
     extra_compile_args={
@@ -50,6 +51,7 @@ if os.environ.get("MSBN_BUILD_NONT", "0") == "1":
             os.path.join(CSRC, "dwconv_grad_kernels_nont_ab.hip"),
             os.path.join(CSRC, "dwconv5x5_kernels_nont_ab.hip"),
             os.path.join(CSRC, "grouped_bn_kernels_nont_ab.hip"),
+            os.path.join(CSRC, "se_kernels_nont_ab.hip"),
         ],
         include_dirs=[CSRC],
         extra_compile_args={
