@@ -14,7 +14,6 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-import oracle64 as o64
 import test_gpu_conv_stats as cs
 import test_gpu_dwconv_stats as d3
 import test_gpu_reduction_edges as edges
@@ -211,19 +210,7 @@ def test_want_flags_and_declines():
 
 def _layer_reference(x, w, gamma, beta, stride, act, gout):
     """d3._layer_reference at kernel 5x5, padding 2."""
-    lv = {k: v.detach().cpu().double().requires_grad_(True) for k, v in
-          dict(x=x, w=w, gamma=gamma, beta=beta).items()}
-    raw = F.conv2d(lv["x"], lv["w"], stride=stride, padding=2,
-                   groups=x.shape[1])
-    yc = cs._Stored.apply(raw, x.dtype)
-    mean, var, _ = o64.stats(yc.detach(), EPS)
-    count = yc.numel() // x.shape[1]
-    z = F.batch_norm(yc, None, None, lv["gamma"], lv["beta"], True, 0.0, EPS)
-    (F.silu(z) if act else z).backward(gout.cpu().double())
-    return {"y": (F.silu(z) if act else z).detach(), "dx": lv["x"].grad,
-            "dw": lv["w"].grad, "dgamma": lv["gamma"].grad,
-            "dbeta": lv["beta"].grad, "running_mean": 0.1 * mean,
-            "running_var": 0.9 + 0.1 * var * count / (count - 1.0)}
+    return d3._layer_reference(x, w, gamma, beta, stride, act, gout, k=5)
 
 
 @pytest.mark.parametrize("dtype", d3.DTYPES)

@@ -164,16 +164,17 @@ def test_declined_inputs_run_the_composition(kind, monkeypatch):
     assert torch.equal(bn.running_var, ref_bn.running_var)
 
 
-def _layer_reference(x, w, gamma, beta, stride, act, gout):
+def _layer_reference(x, w, gamma, beta, stride, act, gout, k=3):
     """float64: silu?(bn(dwconv(x))) from fresh running statistics, the conv
-    output rounded to x's dtype forward and backward.  Outputs / gradients by
-    name; ``conv`` / ``dconv`` / ``dz`` are the stored conv output, the
-    gradient that reaches the convolution and the one that reaches the
-    BatchNorm's output (what a rank-local gradient is made of)."""
+    (``k`` x ``k``, padding ``k // 2``) output rounded to x's dtype forward
+    and backward.  Outputs / gradients by name; ``conv`` / ``dconv`` / ``dz``
+    are the stored conv output, the gradient that reaches the convolution and
+    the one that reaches the BatchNorm's output (what a rank-local gradient
+    is made of)."""
     c = x.shape[1]
     lv = {k: v.detach().cpu().double().requires_grad_(True) for k, v in
           dict(x=x, w=w, gamma=gamma, beta=beta).items()}
-    raw = F.conv2d(lv["x"], lv["w"], stride=stride, padding=1, groups=c)
+    raw = F.conv2d(lv["x"], lv["w"], stride=stride, padding=k // 2, groups=c)
     raw.retain_grad()
     yc = cs._Stored.apply(raw, x.dtype)
     mean, var, _ = o64.stats(yc.detach(), EPS)
